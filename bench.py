@@ -4,21 +4,28 @@ reference's odd-resolution rule) for the 10-primitive smooth-union tree (BASELIN
 SURVEY.md §8(d) "cfg 2 / north-star" recipe), coordinates resident in HBM, field left in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one evaluation of the whole grid. With N > 1 the flat point index is cut into N
 contiguous slabs (= slabs along x), one per rank/GPU, no data-path collective (the path is
-pointwise) -> strong scaling of the same grid. Reassembling the field on every rank (RCCL over xGMI) is
-timed separately after the timed region and reported under "allgather", both after the fact and
-overlapped chunk-wise with the evaluation.
+pointwise) -> strong scaling of the same grid.
 
-The JSON line carries
-  roofline      algorithmic 16 B/point over the live HIP-event kernel time, against the 8 TB/s HBM peak
+A plain run sets up, warms up, times the steps, writes the field of the last step if --dump-outputs
+is given, and prints the line: the headline and its roofline (algorithmic 16 B/point over the live
+HIP-event kernel time, against the 8 TB/s HBM peak). Everything else runs only with --full:
   verified      a random sample of the field the timed region produced, checked against the oracle
   cpu_baseline  the NumPy oracle timed on this host on a bounded x-slab sample of the same grid
   grid_512      the same tree on the 512^3-request grid (north_star names both sizes)
   first_call    cold / warm-cache latency from program creation to the first field (hiprtc JIT)
+  (and stream_probe, other_configs, grid_path, host_path, next_rows; N > 1: "allgather", reassembling
+  the field on every rank (RCCL over xGMI), after the fact and overlapped chunk-wise with the evaluation)
+
+--dump-outputs DIR writes the field the last timed step left in HBM as DIR/field.npy (float32) with the
+flat grid index of every value in DIR/field_index.npy (float64): the whole field up to 4 M points, else a
+fixed seeded sample of at most 4 M points (48 MB), the same for every run with the same arguments. With N > 1
+every rank writes its own slab's sample (field_rank<r>.npy, field_index_rank<r>.npy).
 """
 import argparse
 import json
@@ -58,6 +65,10 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="headline, roofline and verification only (profiling runs)")
     ap.add_argument("--extras-timeout", type=float, default=240.0, help="N > 1: seconds the collective extras may take "
                     "before the line is printed without them")
+    ap.add_argument("--full", action="store_true", help="also run the verification against the oracle and every extra "
+                    "(the --no-* options above choose among them); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the field of the last timed step "
+                    "(a fixed sample of it on large grids) as .npy files into DIR")
     return ap.parse_args()
 
 
@@ -156,6 +167,27 @@ def verify_sample(workload, axes, start, out, count, samples=20000, seed=11):
     return {"points": int(idx.size), "max_rel_err": float(err.max()), "tolerance": 1e-6,
             "violations": int(np.count_nonzero(err > 1e-6)), "against": "oracle/sdf_oracle.evaluate (float64)",
             "what": "random sample of the buffer the timed steps wrote"}
+
+
+DUMP_POINTS = 1 << 22           # 4 M points: 16 MB of float32 field + 32 MB of float64 indices
+
+
+def dump_outputs(path, out, start, count, world, rank, points=DUMP_POINTS, seed=5):
+    """The field the last timed step left in `out` (this rank's `count` points from flat grid index `start`) as
+    `path`/field.npy (float32) and the flat grid index of every value as `path`/field_index.npy (float64, exact):
+    all of the slab up to `points` points, else a sample drawn with a fixed seed (sorted, duplicates dropped), which
+    depends only on `count` and so is the same for every run with the same arguments."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if count <= points:
+        idx = np.arange(count, dtype=np.int64)
+        field = out[:count]
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, count, size=points, dtype=np.int64))
+        field = out[torch.from_numpy(idx).to(out.device)]
+    suffix = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(path, "field%s.npy" % suffix), field.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "field_index%s.npy" % suffix), (idx + start).astype(np.float64))
 
 
 _FIRST_CALL = r"""
@@ -427,6 +459,8 @@ def main():
     torch.cuda.synchronize()
     t_build = time.perf_counter() - t_build
     elapsed, kernel_ms_max, median_ms, min_ms = run.timed(args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run.out, start, count, world, rank)
 
     line = None
     if rank == 0:
@@ -479,6 +513,15 @@ def main():
                                             "implied_clock_ghz_at_this_kernel_time": clock_ghz, "source": VALU_ROOF}
         except Exception:  # noqa: BLE001
             pass
+
+    if not args.full:                                            # a plain run: the headline line and nothing else
+        if world > 1:
+            torch.cuda.synchronize()
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        return
 
     # Whatever happens in the extras, rank 0 prints the headline line and every rank leaves: a watchdog thread stays armed
     # from here until the line has been printed (N > 1: `--extras-timeout` for the collective extras, re-armed for rank 0's
