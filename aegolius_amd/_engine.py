@@ -66,6 +66,10 @@ SIGNATURES = {
     "sdfk_field_select": (_int, [_vp, _i64, _c.c_float, _vp, _i64, _c.POINTER(_i64), _vp, _vp]),
     "sdfk_field_select_finish": (_int, [_i64, _i64, _vp, _i64, _vp, _vp]),
     "sdfk_field_gradient": (_int, [_vp, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp]),
+    "sdfk_field_crossings_2d": (_int, [_vp, _vp, _i64, _i64, _i64, _c.c_double, _c.c_double, _c.c_double, _vp, _vp]),
+    "sdfk_lcwg_eval": (_int, [_int, _vp, _vp, _i64, _i64, _i64, _c.c_double, _c.c_double, _int, _c.c_double, _vp, _vp, _i64,
+                              _vp]),
+    "sdfk_lcwg_old_eval": (_int, [_int, _vp, _i64, _vp, _i64, _c.c_double, _c.c_double, _vp, _i64, _vp]),
     "sdfk_eval_select_scratch": (_sz, [_i64, _i64]),
     "sdfk_eval_device_select": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _c.c_float, _vp, _i64, _c.POINTER(_i64), _vp, _vp, _int]),
     "sdfk_eval_grid_select": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _c.c_float, _vp, _i64, _c.POINTER(_i64),

@@ -279,6 +279,13 @@ def evaluate(closure, p, params, out="vector", resident=False):
         p_arr, grid_axes = start, None
         b = _Builder(start.shape[1], None)
         b.emit("INIT_P")
+    elif name in ("lcwg1_2d", "lcwg1_p1", "lcwg1_m1"):            # LCWG fields: p is uu or (uu, ww), never coordinates
+        from .cores.vector_functions_special import _lcwg_resident
+        if len(params) != 3:
+            raise TypeError("%s() takes 4 positional arguments but %d were given" % (name, 1 + len(params)))
+        p_arr, grid_axes = _lcwg_resident(name, p, *params), None
+        b = _Builder(p_arr.n, None)
+        b.emit("INIT_P")
     elif name in LEAVES:
         if name in STRICT_ARITY and params:
             raise TypeError("%s() takes 1 positional argument but %d were given" % (name, 1 + len(params)))

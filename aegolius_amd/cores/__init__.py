@@ -42,6 +42,8 @@ from .geom_vector import AngledRadialCylindricalVectorField, WindingCylindricalV
 from .geom_vector import VortexCylindricalVectorField, AngledVortexCylindricalVectorField
 from .geom_vector import XVectorField, YVectorField, ZVectorField
 from .geom_vector import VectorFieldFromSDF
+from . import geom_vector_special, vector_functions_special
+from .vector_functions_special import compute_crossings_2d
 
 from .sdf_2D import *  # noqa: F401,F403
 from .sdf_3D import *  # noqa: F401,F403

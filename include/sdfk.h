@@ -296,6 +296,31 @@ int sdfk_field_select(const float* d_field, int64_t n, float threshold, int64_t*
 int sdfk_field_gradient(const float* d_field, int64_t n0, int64_t n1, int64_t n2, int ncomp, int normalize,
                         float* d_vec, int64_t row_stride, void* stream);
 
+/* ---- liquid-crystal waveguide fields ------------------------------------------------------------
+ * cores/vector_functions_special.py on DEVICE fields of n0*n1*n2 fp32 (flat index (i*n1 + j)*n2 + k), synchronous,
+ * float64 arithmetic in numpy's order from the fp32 inputs:
+ *   crossings = compute_crossings_2d (:14-36) of grid plane k = 0: of d_uu, or, when d_ww != NULL, of
+ *               pp = sqrt((2uu/w)^2 + (ww/d)^2). m = min of the plane; c1[i, j] = isclose(s[i, j], m, atol=thr) &
+ *               !isclose(s[i, j-1], m, atol=thr) for j >= 1 (rtol 1e-5 as numpy's default); parity of the running
+ *               count along j; conv_averaging(parity, 5, 2) >= 0.5 (reflect mode). d_sign (DEVICE, n0*n1 int8)
+ *               receives +-1. Bit-identical to the reference on fp32-representable inputs.
+ *   lcwg      = lcwg1_2d (variant 0, :127-161: raw numpy.gradient of uu turned about z by phis, normalised),
+ *               lcwg1_p1 (1, :164-207) and lcwg1_m1 (2, :210-251): normalised gradient of pp, turned about
+ *               e2 = vec x e1 by phis, then about e1 = |(-vec_y, vec_x, 0)| by -2 alpha, alpha = +-arctan2(2ww/d^2,
+ *               8uu/w^2), normalised; phis = sign * (clip(value, 0, 1) pi + pi/2), value = 2uu/w (2D) or pp.
+ *               sign_kind 0: sign = sign_value everywhere; 1: d_sign is the int8 plane of sdfk_field_crossings_2d
+ *               (point p takes entry p / n2); 2: d_sign holds one fp32 number per point. Every axis needs >= 2
+ *               points; d_ww may be NULL for variant 0. d_vec: three rows of row_stride floats. 20 B/point of traffic
+ *               for variants 1 and 2 (uu, ww in, 3 rows out), 16 for variant 0.
+ *   lcwg old  = lcwg1_2d_old / lcwg1_p1_old / lcwg1_m1_old (:39-124), pointwise: d_r holds three rows of r_stride
+ *               floats (the positions r), d_uu n numbers. */
+int sdfk_field_crossings_2d(const float* d_uu, const float* d_ww, int64_t n0, int64_t n1, int64_t n2, double w, double d,
+                            double thr, signed char* d_sign, void* stream);
+int sdfk_lcwg_eval(int variant, const float* d_uu, const float* d_ww, int64_t n0, int64_t n1, int64_t n2, double w, double d,
+                   int sign_kind, double sign_value, const void* d_sign, float* d_vec, int64_t row_stride, void* stream);
+int sdfk_lcwg_old_eval(int variant, const float* d_r, int64_t r_stride, const float* d_uu, int64_t n, double w, double d,
+                       float* d_vec, int64_t row_stride, void* stream);
+
 /* ---- vector-field programs ----------------------------------------------------------------------
  * The reference's vector-field path (cores/geom.py:213-362 VectorField; cores/vector_functions.py:15-127 field
  * definitions; cores/modifications.py:1666-1975 ModifyVectorObject; cores/vector_modification_functions.py:14-160)
