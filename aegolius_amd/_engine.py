@@ -99,6 +99,10 @@ SIGNATURES = {
     "sdfk_event_record": (_int, [_vp, _vp]),
     "sdfk_event_elapsed_ms": (_int, [_vp, _vp, _fp]),
     "sdfk_stream_probe": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "sdfk_dual_has_rule": (_int, [_int]),
+    "sdfk_program_jvp_check": (_int, [_vp, _c.POINTER(_int)]),
+    "sdfk_eval_jvp_device": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _i64, _vp]),
+    "sdfk_value_jvp_device": (_int, [_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -33,7 +33,8 @@ class LoweringError(Exception):
 
 
 class LoweredProgram:
-    __slots__ = ("code", "params", "tables", "result_reg", "n_creg", "n_vreg", "cull_sites", "cull_k", "stage_params")
+    __slots__ = ("code", "params", "tables", "result_reg", "n_creg", "n_vreg", "cull_sites", "cull_k", "stage_params",
+                 "params64")
 
     def __init__(self, code, params, tables, result_reg, n_creg, n_vreg, cull_sites=None, cull_k=None):
         self.code, self.params, self.tables = code, params, tables
@@ -42,6 +43,7 @@ class LoweredProgram:
         self.cull_sites = np.zeros((0, 5), dtype=np.uint32) if cull_sites is None else cull_sites
         self.cull_k = np.zeros(0, dtype=np.float32) if cull_k is None else cull_k
         self.stage_params = ()     # stage programs: the geometry parameters the staged operator's closure is called with
+        self.params64 = None       # the parameter table before its rounding to fp32 (set by Lowerer.finish)
 
     def key(self):
         return (self.code.tobytes(), self.params.tobytes(), self.tables.tobytes(), self.result_reg,
@@ -72,7 +74,12 @@ class StageStop(Exception):
 
 
 class Lowerer:
-    def __init__(self):
+    def __init__(self, shortcuts=True):
+        # shortcuts=False: never choose an instruction form from a parameter's VALUE (aliased identity transforms, XLATE for
+        # R = I / s = 1, skipped VSCALE for s = 1, composed affine maps, the positive-map fold of VSIGN / VHARDBIN, flattened
+        # hard unions). The program's structure then depends on the tree alone, so that it stays the same when a parameter
+        # moves (aegolius_amd.autodiff differentiates the lowering). The field is the same up to fp32 rounding.
+        self.shortcuts = shortcuts
         self.code = []
         self.params = []
         self.tables = []            # chunks (float64 arrays), concatenated by finish(); offsets count floats
@@ -214,6 +221,8 @@ class Lowerer:
         params = [float(x) for x in np.asarray(params, dtype=np.float64).ravel()]
         if len(params) != info.nparams:
             raise LoweringError("%s expects %d parameters, got %d" % (opname, info.nparams, len(params)))
+        if not self.shortcuts:
+            _fold = False
         if _fold and opname in ("VSIGN", "VHARDBIN") and self._fold_positive_map(opname, a, b, params):
             return
         if _fold and opname in self._AFFINE:
@@ -268,10 +277,12 @@ class Lowerer:
         # the largest subtrees first if there are more sites than mask bits
         sites = sorted(self.cull, key=lambda r: -((r[2] - r[1]) + (r[4] - r[3])))[:_lip.MAX_SITES]
         sites.sort(key=lambda r: r[0])
-        return LoweredProgram(np.asarray(self.code, dtype=np.uint32).reshape(-1, 2), params, tables, vreg,
-                              self.n_creg, self.n_vreg,
-                              np.asarray([r[:5] for r in sites], dtype=np.uint32).reshape(-1, 5),
-                              np.asarray([r[5] for r in sites], dtype=np.float32))
+        low = LoweredProgram(np.asarray(self.code, dtype=np.uint32).reshape(-1, 2), params, tables, vreg,
+                             self.n_creg, self.n_vreg,
+                             np.asarray([r[:5] for r in sites], dtype=np.uint32).reshape(-1, 5),
+                             np.asarray([r[5] for r in sites], dtype=np.float32))
+        low.params64 = np.asarray(self.params, dtype=np.float64)
+        return low
 
     # ---- coordinate helpers ----
     def writable(self, creg, mode):
@@ -299,7 +310,7 @@ class Lowerer:
             raise ValueError("rotation matrix must have shape (3, 3); got %r" % (R.shape,))
         t = np.asarray(node.center, dtype=np.float64).reshape(3)
         s = node.scale
-        pushed = _push_transform_into_members(node)
+        pushed = _push_transform_into_members(node) if self.shortcuts else None
         if pushed is not None:
             # a large hard union that was moved / rotated / rescaled as a whole (value modifications on top included):
             # every member behind that transform (see _flatten_hard), so that the members still start from the input
@@ -308,8 +319,8 @@ class Lowerer:
             if s != 1:
                 self.emit("VSCALE", v, v, params=[s])
             return v
-        ident_r = np.array_equal(R, np.eye(3))
-        unit_s = (s == 1)
+        ident_r = np.array_equal(R, np.eye(3)) and self.shortcuts
+        unit_s = (s == 1) and self.shortcuts
         if ident_r and unit_s and not np.any(t):
             # (I·co)/1.0 - 0 is a bit-exact copy in the reference: alias the register instead
             c, inner_mode = creg, (OWNED if mode == OWNED else FROZEN)
@@ -398,7 +409,7 @@ class Lowerer:
                     raise TypeError("%s takes exactly 2 objects (%d given)" % (op, len(kids)))
             else:
                 raise KeyError(op)
-        if not expr.parametric and opcode == "VSUBTRACT" and not _holds_combiner(kids[0]):
+        if self.shortcuts and not expr.parametric and opcode == "VSUBTRACT" and not _holds_combiner(kids[0]):
             # (a body that is a combination of its own stays an operand: the chain kernels then run the union as a chain
             #  and body and subtraction as the REST of the program, sdfk_codegen.cpp chain_analyse)
             holes = _subtracted_union(kids[1])
@@ -407,7 +418,7 @@ class Lowerer:
                 # an n-ary INTERSECT of the body and the negated members (negation is exact) — one chain instead of a
                 # chain inside an operand, which the chain kernels do not take
                 kids, opcode = (kids[0],) + holes, "VMAX"
-        if not expr.parametric and opcode in ("VMIN", "VMAX"):
+        if self.shortcuts and not expr.parametric and opcode in ("VMIN", "VMAX"):
             kids = _flatten_hard(kids, opcode)
         acc = None
         first = len(self.code)
@@ -742,14 +753,14 @@ def _deep(fn):
     return box["value"]
 
 
-def lower_geometry(node, fields=None, stop_at=None, probe_axis=None):
+def lower_geometry(node, fields=None, stop_at=None, probe_axis=None, shortcuts=True):
     """Lower `node.create(co)` to a program. `fields` / `stop_at` / `probe_axis`: stage programs of a tree with
-    grid-neighbourhood operators (see _eval._run_staged)."""
-    return _deep(lambda: _lower_geometry(node, fields, stop_at, probe_axis))
+    grid-neighbourhood operators (see _eval._run_staged). `shortcuts=False`: see Lowerer."""
+    return _deep(lambda: _lower_geometry(node, fields, stop_at, probe_axis, shortcuts))
 
 
-def _lower_geometry(node, fields, stop_at, probe_axis):
-    L = _staged(Lowerer(), fields, stop_at, probe_axis)
+def _lower_geometry(node, fields, stop_at, probe_axis, shortcuts=True):
+    L = _staged(Lowerer(shortcuts), fields, stop_at, probe_axis)
     try:
         v = L.lower_node(node, 0, OWNED)
     except StageStop as stop:

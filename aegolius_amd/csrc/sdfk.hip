@@ -2398,3 +2398,4 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_vector.inc"
 #include "sdfk_hosttree.inc"
 #include "sdfk_lcwg.inc"
+#include "sdfk_dual.inc"

@@ -394,6 +394,25 @@ int sdfk_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* synchron
 /* plain (3,n)->(n) streaming kernel out = x+y+z with the same access pattern: measured HBM ceiling */
 int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_stride, float* d_out, void* stream);
 
+
+/* ---- forward-mode derivatives (dual numbers; csrc/sdfk_dual.inc, rules in csrc/sdfk_dualdev.h) ---------------------
+ * A program is evaluated on dual numbers: next to its value, K = 1..4 tangents per point. Parameter mode: d_dparams holds
+ * K rows of n_params floats (the program's parameter count), row k = d P / d theta_k; the coordinates carry no tangent.
+ * Point mode (seed_points = 1, K = 3): the input point's tangents are the unit vectors, d_dparams is K rows of zeros,
+ * and the tangents are the spatial gradient. d_value: n floats; d_tangent: K rows of tangent_stride floats.
+ * Every instruction is evaluated (no culling, no code specialisation). */
+/* 1 if opcode op has a dual rule, else 0 (the single table in csrc/sdfk_dualdev.h) */
+int sdfk_dual_has_rule(int op);
+/* 0: the program can be differentiated; 1: instruction *first_bad_op has no dual rule; 2: its register files exceed the
+ * dual kernel's (16 coordinate / 8 value registers); < 0 on error. sdfk_last_error names the cause. */
+int sdfk_program_jvp_check(sdfk_program* prog, int* first_bad_op);
+int sdfk_eval_jvp_device(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, const float* d_dparams, int k,
+                         int seed_points, float* d_value, float* d_tangent, int64_t tangent_stride, void* stream);
+/* One value operation (a V_V opcode with a dual rule, P its parameter block) on n (value, tangent) pairs: the chain rule
+ * through a post-processing map, parameter tangents zero. */
+int sdfk_value_jvp_device(int op, const float* P, const float* d_v, const float* d_t, int64_t n, float* d_out_v,
+                          float* d_out_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
