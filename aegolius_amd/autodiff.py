@@ -12,6 +12,8 @@ The "function" being differentiated is a BUILDER: a Python callable that takes t
     value, tan  = jvp(builder, co, primals, tangents)                      # directional derivative, (N,)
     value, g    = value_and_grad_points(geometry, co)                      # spatial gradient, (3, N)
     out, out_t  = post_jvp(name, field, field_tangent, *params)            # chain rule through a post-processing map
+    value, g    = vjp(builder, co, primals, cotangent, argnums=0)          # Σ_i c_i ∂f_i/∂θ, one adjoint pass
+    loss, g     = value_and_grad_sse(builder, co, primals, target)         # Σ (f - t)² and its gradient, one pass
 
 Layout: Jacobians are (m, N) — derivative first, points second, the package's (D, N) convention. That is the TRANSPOSE
 of JAX's jacfwd layout, which puts the output dimension (N) first.
@@ -21,6 +23,10 @@ in float64 (aegolius_amd._lower). The builder's geometry is lowered at p, p + h 
 shortcut-free mode (no instruction form is chosen from a parameter's value) and dP_k = (P+ - P-) / 2h is taken in
 float64, rounded once to fp32. The program must be the same at all three points (else StructureError), and the two
 one-sided differences must agree (else a jump in the host arithmetic: StructureError).
+
+Reverse mode (vjp, value_and_grad_sse): one pass of the adjoint kernel (csrc/sdfk_adjoint.inc) evaluates the program with
+a restore tape, back-propagates a cotangent per point and reduces P̄ = Σ_i c_i ∂f_i/∂P on the device in float64; the host
+applies θ̄ = dP/dθ · P̄ with the float64 rows of parameter_tangents (not rounded). Gradients have JAX's grad structure.
 """
 import ctypes
 import inspect
@@ -428,3 +434,108 @@ def post_jvp(name, field, field_tangent, *params):
     dv.free()
     dt.free()
     return _host(out_v).reshape(shape), _host(out_t).reshape(shape)
+
+
+# ---------------------------------------------------------------------------------------------------
+# reverse mode
+# ---------------------------------------------------------------------------------------------------
+def adjoint_limits():
+    """(restore-tape floats per point, parameters per program) the adjoint kernel accepts."""
+    tape, params = ctypes.c_int(0), ctypes.c_int(0)
+    _engine.lib().sdfk_vjp_limits(ctypes.byref(tape), ctypes.byref(params))
+    return tape.value, params.value
+
+
+def _adjoint_program(low, origin):
+    """The native program of a lowering, checked for dual rules and the adjoint kernel's tape and parameter limits."""
+    prog = _program(low, origin)
+    tape = ctypes.c_int64(0)
+    rc = _engine.lib().sdfk_program_vjp_check(prog.handle, None, ctypes.byref(tape))
+    if rc == 3:
+        raise UnsupportedOpError("program too large for the adjoint kernel: its restore tape takes %d floats per point, "
+                                 "%d at most" % (tape.value, adjoint_limits()[0]))
+    if rc == 4:
+        raise UnsupportedOpError("program too large for the adjoint kernel: %d parameters, %d at most"
+                                 % (low.params.size, adjoint_limits()[1]))
+    _engine.check(rc, "sdfk_program_vjp_check")
+    return prog
+
+
+def _point_count(co):
+    """N of what _Coords accepts, on the host (nothing touches the GPU)."""
+    if isinstance(co, _engine.DeviceVectorField):
+        return int(co.n)
+    axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
+    if axes is not None:
+        return int(np.prod([np.asarray(a).size for a in axes]))
+    shape = np.shape(co)
+    if len(shape) != 2 or shape[0] != 3:
+        raise ValueError("coordinates must have shape (3, N); got %r" % (shape,))
+    return int(shape[1])
+
+
+def _check_size(x, n, what):
+    size = x.n if isinstance(x, _engine.DeviceField) else np.asarray(x).size
+    if size != n or (not isinstance(x, _engine.DeviceField) and np.ndim(x) != 1):
+        raise ValueError("%s must be an (N,) array or a DeviceField of N = %d points; got %s" %
+                         (what, n, size if isinstance(x, _engine.DeviceField) else np.shape(x)))
+
+
+def chain_rule(rows, pbar, layout, argnums):
+    """θ̄_k = Σ_j P̄_j dP_j/dθ_k in float64, shaped like JAX's grad: a float for a scalar primal, an (m,) array for a 1-D
+    one, a tuple of those for a tuple `argnums`. rows: (channels, n_params) float64 (parameter_tangents)."""
+    theta = np.asarray(rows, dtype=np.float64).dot(np.asarray(pbar, dtype=np.float64)) if len(rows) else np.zeros(0)
+    grads = [float(theta[first]) if scalar else theta[first:first + count].copy() for first, count, scalar in layout]
+    return grads[0] if isinstance(argnums, (int, np.integer)) else tuple(grads)
+
+
+def _reverse(prog, co, d_in, mode, generic, n_params):
+    """One adjoint launch -> (value DeviceField, P̄ (n_params,) float64, loss)."""
+    _engine.require_gpu()
+    L = _engine.lib()
+    vp = _engine._vp
+    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
+    coords = _Coords(co)
+    owned = None
+    try:
+        if not isinstance(d_in, _engine.DeviceField):
+            owned = d_in = _engine.DeviceField.from_host(np.asarray(d_in, dtype=np.float32), config.device)
+        value = _engine.DeviceField(coords.n, config.device)
+        pbar = np.zeros(n_params, dtype=np.float64)
+        loss = ctypes.c_double(0.0)
+        _engine.check(L.sdfk_eval_vjp_device(prog.handle, vp(coords.ptr), coords.n, coords.stride, vp(d_in.ptr), mode,
+                                             1 if generic else 0, vp(value.ptr), _engine._ptr(pbar), ctypes.byref(loss),
+                                             None), "sdfk_eval_vjp_device")
+        return value, pbar, loss.value
+    finally:
+        coords.free()
+        if owned is not None:
+            owned.free()
+
+
+def _grad(builder, co, primals, d_in, argnums, mode, generic, what):
+    n = _point_count(co)
+    _check_size(d_in, n, what)
+    low, origin, rows, _chans, layout = parameter_tangents(builder, primals, argnums)
+    prog = _adjoint_program(low, origin)
+    value, pbar, loss = _reverse(prog, co, d_in, mode, generic, low.params.size)
+    return value, chain_rule(rows, pbar, layout, argnums), loss
+
+
+def vjp(builder, co, primals, cotangent, argnums=0, resident=False, generic_rules=False):
+    """(field, Σ_i c_i ∂f_i/∂θ) for the primals named by `argnums`, from ONE pass of the adjoint kernel whatever their
+    number. `builder`, `co`, `primals`, `argnums` as in value_and_jacfwd; `cotangent` c: an (N,) host array or a
+    DeviceField. Returns (value, grads): value (N,) host float32, or a DeviceField with resident=True; grads in JAX's
+    grad structure — a float per scalar primal, a float64 (m,) array per 1-D primal, a tuple for a tuple `argnums`.
+    generic_rules=True derives every instruction's product from its dual rule (no hand-written adjoints): a check."""
+    value, grads, _loss = _grad(builder, co, primals, cotangent, argnums, 0, generic_rules, "the cotangent")
+    return (value if resident else _host(value)), grads
+
+
+def value_and_grad_sse(builder, co, primals, target, argnums=0, generic_rules=False):
+    """(L, ∂L/∂θ) of L = Σ_i (f_i - t_i)² in one adjoint pass: the field, the cotangent 2 (f_i - t_i) (in registers) and
+    the loss (float64) come from the same launch. `target`: an (N,) host array (rounded to float32) or a DeviceField;
+    the rest as in vjp. This is the `value_and_grad(worker)` of the reference's optimisation examples."""
+    value, grads, loss = _grad(builder, co, primals, target, argnums, 1, generic_rules, "the target")
+    value.free()
+    return loss, grads

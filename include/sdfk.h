@@ -413,6 +413,21 @@ int sdfk_eval_jvp_device(sdfk_program* prog, const float* d_co, int64_t n, int64
 int sdfk_value_jvp_device(int op, const float* P, const float* d_v, const float* d_t, int64_t n, float* d_out_v,
                           float* d_out_t, void* stream);
 
+/* ---- reverse-mode derivatives (adjoint; csrc/sdfk_adjoint.inc, rules derived from csrc/sdfk_dualdev.h) --------------
+ * One pass evaluates the program at n points with a restore tape and back-propagates a cotangent c_i per point; the
+ * parameter adjoints P̄_j = sum_i c_i d f_i / d P_j are reduced on the device in float64 (deterministic order).
+ * mode 0: d_in holds the cotangent c (n floats). mode 1 (sum of squares): d_in holds a target t (n floats), the cotangent
+ * is 2 (f_i - t_i) and *h_loss receives sum_i (f_i - t_i)^2 (float64). d_out_value (n floats) and h_loss may be null.
+ * h_pbar receives n_params doubles. flags bit 0: generic rules only (every product derived from the dual rule). Host
+ * pointers h_pbar / h_loss are written before the call returns (the call waits for its stream). */
+/* 0: the program can be back-propagated; 1 / 2: as sdfk_program_jvp_check; 3: its restore tape exceeds the kernel's
+ * (*tape_floats receives its size in floats per point); 4: more parameters than the kernel's accumulator holds. */
+int sdfk_program_vjp_check(sdfk_program* prog, int* first_bad_op, int64_t* tape_floats);
+/* the adjoint kernel's limits: restore-tape floats per point, parameters per program */
+int sdfk_vjp_limits(int* tape_floats, int* max_params);
+int sdfk_eval_vjp_device(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, const float* d_in, int mode,
+                         int flags, float* d_out_value, double* h_pbar, double* h_loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
