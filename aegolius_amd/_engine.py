@@ -106,6 +106,10 @@ SIGNATURES = {
     "sdfk_program_vjp_check": (_int, [_vp, _c.POINTER(_int), _c.POINTER(_i64)]),
     "sdfk_vjp_limits": (_int, [_c.POINTER(_int), _c.POINTER(_int)]),
     "sdfk_eval_vjp_device": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp]),
+    "sdfk_points_bin": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "sdfk_points_extent": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "sdfk_points_fill": (_int, [_vp, _i64, _i64, _i64, _int, _i64, _i64, _i64, _vp]),
+    "sdfk_points_widen": (_int, [_vp, _i64, _int, _vp, _vp]),
 }
 
 

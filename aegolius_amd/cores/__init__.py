@@ -4,11 +4,12 @@ from . import post_processing
 from . import triangulation_functions
 from .combine import CombineGeometry
 from .combine import smoothmin_poly2, smoothmin_poly3, smoothmax_boltz
-from .transformations import EuclideanTransform
+from .transformations import EuclideanTransform, EuclideanTransformPoints
 from .modifications import ModifyObject
-from .geom import GenericGeometry, VectorField
+from .geom import GenericGeometry, Points, VectorField
 from .modifications import ModifyVectorObject
 
+from .post_processing import PostProcess
 from .post_processing import sigmoid_falloff, positive_sigmoid_falloff, capped_exponential
 from .post_processing import hard_binarization, linear_falloff
 from .post_processing import relu, smooth_relu, slowstart

@@ -9,7 +9,8 @@ import numpy as np
 
 from .._eval import evaluate_geometry
 from .modifications import ModifyObject, ModifyVectorObject
-from .transformations import EuclideanTransform
+from .helper_functions import resolution_conversion  # noqa: F401  (the reference's geom namespace)
+from .transformations import EuclideanTransform, EuclideanTransformPoints
 
 
 class GenericGeometry(EuclideanTransform, ModifyObject):
@@ -54,6 +55,54 @@ class GenericGeometry(EuclideanTransform, ModifyObject):
         pts = np.zeros((3, inside.size))
         pts[:2, :] = np.asarray(co)[:2, inside]
         return pts
+
+
+class Points(EuclideanTransformPoints):
+    """A point cloud (reference cores/geom.py:77-210).
+
+    Args:
+        points: The point cloud (D, N); an array with fewer columns than rows is taken as (N, D) and transposed.
+    """
+
+    def __init__(self, points):
+        EuclideanTransformPoints.__init__(self)
+        self._points = np.asarray(points)
+        if self._points.size > 0 and self._points.shape[1] < self._points.shape[0]:
+            self._points = self._points.T
+
+    @property
+    def cloud(self):
+        """The transformed point cloud (D, N), computed on the host."""
+        return self.apply(self._points)
+
+    def from_image(self, greyscale_image, image_dimensions, binary_threshold=0.5):
+        """Replace the cloud by the pixels of `greyscale_image` whose brightness (relative to the brightest pixel) is at
+        most `binary_threshold`, placed on an image_dimensions[0] x image_dimensions[1] rectangle centred on the origin
+        (z = 0). Host numpy: a few megapixels at most, a GPU version would not pay."""
+        data = np.asarray(greyscale_image)
+        data = data.astype(float) / np.amax(data)
+        data = np.flip(data, axis=0).T
+        mask = data <= binary_threshold
+        lattice = np.asarray(np.meshgrid(np.linspace(-image_dimensions[0] / 2, image_dimensions[0] / 2, data.shape[0]),
+                                         np.linspace(-image_dimensions[1] / 2, image_dimensions[1] / 2, data.shape[1]),
+                                         indexing="ij"))
+        pts = np.zeros((3, np.count_nonzero(mask)))
+        pts[:2, :] = lattice[:, mask]
+        self._points = pts
+
+    def to_image(self, co_size, co_resolution, extend):
+        """Voxel occupancy of the cloud: (res_x, res_y, res_z) float64 of 0 / 1 (numpy.histogramdd(cloud.T, bins,
+        range) > 0 over the box co_size centred on the origin), then extended along each entry of `extend` ("-X", "+X",
+        "-Y", "+Y", "-Z", "+Z", in the given order) by repeating the first / last occupied plane outwards. Binning,
+        extension and widening run on the GPU (csrc/sdfk_points.inc)."""
+        from .._points import to_image
+        return to_image(self.cloud, co_size, co_resolution, extend)
+
+    def to_image_resident(self, co_size, co_resolution, extend, device=0):
+        """to_image(), but the grid stays in HBM: an `aegolius_amd.DeviceField` of res_x res_y res_z float32 0 / 1
+        values in C order (at 1025^3 the host result of to_image is 8.6 GB of float64)."""
+        from .._points import to_image
+        return to_image(self.cloud, co_size, co_resolution, extend, resident=True, device=device)
 
 
 class VectorField(ModifyVectorObject):

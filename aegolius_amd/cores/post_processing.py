@@ -4,10 +4,89 @@ instructions a tree would use (`ModifyObject.sigmoid_falloff` etc. lower to the 
 also be an `aegolius_amd.DeviceField`, and then the result stays in HBM. `conv_averaging` / `conv_edge_detection`
 take a GRID-shaped (2-D / 3-D) array like the reference and run the device stencil kernels.
 
-The `PostProcess` closure-builder class of the reference (:13-375) duplicates the `ModifyObject` post-process
-methods and is outside the scope of this package.
+`PostProcess` (:13-375) builds the same chains as the `ModifyObject` post-process methods, on a bare scalar field:
+every method records a symbolic step (`_ir.ModSDF`, the node `ModifyObject` records) instead of a Python closure, so
+`GenericGeometry(pp.processed_geo_object, ...)` lowers the whole chain to one fused GPU program.
 """
 from .. import _eval
+from .._ir import ModSDF
+from .._lower import as_expr
+
+
+class PostProcess:
+    """Post-processing operations applied to a scalar field (reference :13-375).
+
+    Attributes:
+        unprocessed_geo_object: The field as given.
+        processed_geo_object: The field with the operations applied so far; callable as
+            `processed_geo_object(co, *params)`, and an SDF that GenericGeometry accepts.
+
+    Args:
+        geo_object: Scalar field `geo_object(co, *params)`: an `sdf_*` function, a modification closure or
+            `obj.propagate`.
+    """
+
+    def __init__(self, geo_object):
+        self._pmod = []
+        self.unprocessed_geo_object = geo_object
+        self.processed_geo_object = geo_object
+
+    post_processing_operations = property(lambda self: self._pmod,
+                                          doc="Chronological list of applied post-processing operations.")
+    processed_object = property(lambda self: self.processed_geo_object, doc="The post-processed field.")
+    unprocessed_object = property(lambda self: self.unprocessed_geo_object, doc="The field as given.")
+
+    def _step(self, name, args, label=None):
+        self._pmod.append(label or name)
+        node = ModSDF(name, args, as_expr(self.processed_geo_object))
+        self.processed_geo_object = node
+        return node
+
+    def sigmoid_falloff(self, amplitude, width):
+        return self._step("sigmoid_falloff", {"amplitude": amplitude, "width": width})
+
+    def positive_sigmoid_falloff(self, amplitude, width):
+        return self._step("positive_sigmoid_falloff", {"amplitude": amplitude, "width": width})
+
+    def capped_exponential(self, amplitude, width):
+        return self._step("capped_exponential", {"amplitude": amplitude, "width": width})
+
+    def hard_binarization(self, threshold):
+        return self._step("hard_binarization", {"threshold": threshold})
+
+    def linear_falloff(self, amplitude, width):
+        return self._step("linear_falloff", {"amplitude": amplitude, "width": width})
+
+    def relu(self, width):
+        return self._step("relu", {"width": width})
+
+    def smooth_relu(self, smooth_width, width=1, threshold=0.01):
+        return self._step("smooth_relu", {"smooth_width": smooth_width, "width": width, "threshold": threshold})
+
+    def slowstart(self, smooth_width, width=1, threshold=0.01, ground=True):
+        return self._step("slowstart", {"smooth_width": smooth_width, "width": width, "threshold": threshold,
+                                        "ground": ground})
+
+    def gaussian_boundary(self, amplitude, width):
+        return self._step("gaussian_boundary", {"amplitude": amplitude, "width": width})
+
+    def gaussian_falloff(self, amplitude, width):
+        return self._step("gaussian_falloff", {"amplitude": amplitude, "width": width})
+
+    def conv_averaging(self, kernel_size, iterations, co_resolution):
+        """Box filter over the field reshaped to the grid co_resolution (device stencil); the result is flat."""
+        return self._step("conv_averaging", {"kernel_size": kernel_size, "iterations": iterations,
+                                             "co_resolution": co_resolution})
+
+    def conv_edge_detection(self, co_resolution):
+        """3 x 3 edge stencil over the field reshaped to the grid; the result keeps the grid's shape, as in the
+        reference."""
+        return self._step("conv_edge_detection", {"co_resolution": co_resolution})
+
+    def custom_post_process(self, function, parameters, post_process_name="custom"):
+        """function(u, *parameters), called on the host with the field computed so far."""
+        return self._step("custom_post_process", {"function": function, "parameters": parameters},
+                          label=post_process_name)
 
 
 def sigmoid_falloff(u, amplitude, width):

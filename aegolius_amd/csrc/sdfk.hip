@@ -2400,3 +2400,4 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_lcwg.inc"
 #include "sdfk_dual.inc"
 #include "sdfk_adjoint.inc"
+#include "sdfk_points.inc"

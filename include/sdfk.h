@@ -428,6 +428,20 @@ int sdfk_vjp_limits(int* tape_floats, int* max_params);
 int sdfk_eval_vjp_device(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, const float* d_in, int mode,
                          int flags, float* d_out_value, double* h_pbar, double* h_loss, void* stream);
 
+/* ---- point cloud -> voxel occupancy (Points.to_image; csrc/sdfk_points.inc) ------------------------------------------
+ * The grid is rx * ry * rz bytes, C order. d_cloud: (3, n) float64 rows row_stride apart; d_edges: the float64 bin
+ * edges of the three axes back to back (rx + 1, ry + 1, rz + 1 values, numpy.histogramdd's). sdfk_points_bin zeroes the
+ * grid and writes 1 into every voxel that holds a point (numpy's outliers and NaN dropped). sdfk_points_extent writes
+ * rx + ry + rz "plane holds a voxel" bytes (x planes, then y, then z; rz <= 65536). sdfk_points_fill makes planes
+ * [lo, hi) of axis 0 / 1 / 2 copies of plane src (src outside the range). sdfk_points_widen writes the grid as 0.0 / 1.0:
+ * kind 0 float64, kind 1 float32. All four are asynchronous on the stream. */
+int sdfk_points_bin(const double* d_cloud, int64_t n, int64_t row_stride, const double* d_edges, int64_t rx, int64_t ry,
+                    int64_t rz, unsigned char* d_grid, void* stream);
+int sdfk_points_extent(const unsigned char* d_grid, int64_t rx, int64_t ry, int64_t rz, unsigned char* d_flags, void* stream);
+int sdfk_points_fill(unsigned char* d_grid, int64_t rx, int64_t ry, int64_t rz, int axis, int64_t src, int64_t lo, int64_t hi,
+                     void* stream);
+int sdfk_points_widen(const unsigned char* d_grid, int64_t n, int kind, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
