@@ -11,5 +11,6 @@ program and runs it as ONE fused per-point HIP kernel (libsdfk.so, gfx950). Ther
 from ._eval import config  # noqa: F401
 from ._engine import DeviceField, DeviceVectorField  # noqa: F401
 from . import cores  # noqa: F401
+from . import mesh  # noqa: F401
 
 __version__ = "0.1.0"

@@ -110,6 +110,14 @@ SIGNATURES = {
     "sdfk_points_extent": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "sdfk_points_fill": (_int, [_vp, _i64, _i64, _i64, _int, _i64, _i64, _i64, _vp]),
     "sdfk_points_widen": (_int, [_vp, _i64, _int, _vp, _vp]),
+    "sdfk_field_isosurface_scratch": (_sz, [_i64, _i64, _i64]),
+    "sdfk_field_isosurface": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64), _vp,
+                                     _vp]),
+    "sdfk_field_isosurface_finish": (_int, [_vp, _i64, _i64, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp,
+                                            _vp]),
+    "sdfk_field_contour2d_scratch": (_sz, [_i64, _i64]),
+    "sdfk_field_contour2d": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64), _vp, _vp]),
+    "sdfk_field_contour2d_finish": (_int, [_vp, _i64, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
 }
 
 

@@ -2401,3 +2401,4 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_dual.inc"
 #include "sdfk_adjoint.inc"
 #include "sdfk_points.inc"
+#include "sdfk_mesh.inc"

@@ -1,0 +1,303 @@
+"""Isosurface meshes and 2-D contours of scalar fields, extracted on the GPU (kernels: csrc/sdfk_mesh.inc).
+
+    from aegolius_amd import mesh
+    m = mesh.from_geometry(geometry, (2, 2, 2), (257, 257, 257))      # or mesh.isosurface(device_field, co)
+    m.compute_normals(geometry)
+    m.write_ply("part.ply")
+
+The field stays in HBM (a DeviceField, or a host array uploaded once); only the mesh crosses PCIe.
+
+Output definition (the kernels and tests/mesh_reference.py implement exactly this):
+  * A grid point is inside if f <= level. NaN is outside.
+  * Point (i, j, k) owns its grid edges in +x, +y and +z. There is one vertex per edge whose two ends differ in the inside
+    test, ordered by the owning point's linear index (C order, z fastest), then by axis. Along the edge's axis the vertex
+    sits at x = xa + t * (xb - xa), t = (level - fa) / (fb - fa), in float32 and this operation order, a the lower end;
+    the other coordinates are the axis values. If one end is NaN, the vertex is put at the other end.
+  * Triangles are ordered by cell (the index of its minimum corner in the (nx-1)(ny-1)(nz-1) cells, C order), then by
+    the order of the generated case table (aegolius_amd/_mctable.py: one face rule, diagonal inside corners separated,
+    so that the mesh is watertight). (v1 - v0) x (v2 - v0) points toward increasing f.
+  * 2-D: the same per square (16 cases); point (i, j) owns its +x and +y edges; each segment (a, b) has the inside on
+    its left, so an inside region is bounded counter-clockwise and a hole clockwise.
+"""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _engine
+
+
+class Mesh:
+    """A triangle mesh: vertices (V, 3) float32, faces (F, 3) int64, normals None or (V, 3) float32."""
+
+    def __init__(self, vertices, faces, normals=None):
+        self.vertices = vertices
+        self.faces = faces
+        self.normals = normals
+
+    def __repr__(self):
+        return "Mesh(%d vertices, %d faces)" % (len(self.vertices), len(self.faces))
+
+    def compute_normals(self, geometry):
+        """Unit gradient of `geometry` at every vertex (autodiff.value_and_grad_points, normalised on the host).
+        Raises that function's UnsupportedOpError for trees without a dual rule."""
+        from .autodiff import value_and_grad_points
+        _, grad = value_and_grad_points(geometry, np.ascontiguousarray(self.vertices.T, dtype=np.float32))
+        g = np.asarray(grad, dtype=np.float64).reshape(3, -1).T
+        norm = np.linalg.norm(g, axis=1, keepdims=True)
+        self.normals = np.ascontiguousarray(np.divide(g, norm, out=np.zeros_like(g), where=norm > 0), dtype=np.float32)
+        return self.normals
+
+    def write_obj(self, path):
+        v = np.asarray(self.vertices, dtype=np.float32)
+        with open(path, "w") as f:
+            f.write("# %d vertices, %d faces\n" % (len(v), len(self.faces)))
+            if len(v):
+                np.savetxt(f, v, fmt="v %.9g %.9g %.9g")
+            if self.normals is not None and len(v):
+                np.savetxt(f, np.asarray(self.normals, dtype=np.float32), fmt="vn %.9g %.9g %.9g")
+            if len(self.faces):
+                fi = np.asarray(self.faces, dtype=np.int64) + 1
+                if self.normals is not None:
+                    np.savetxt(f, np.repeat(fi, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
+                else:
+                    np.savetxt(f, fi, fmt="f %d %d %d")
+
+    def write_ply(self, path):
+        """Binary little-endian PLY: float x y z (and nx ny nz), faces as uchar-counted int lists."""
+        v = np.asarray(self.vertices, dtype="<f4")
+        if len(v) > 0x7fffffff:
+            raise ValueError("PLY int vertex indices hold fewer than 2^31 vertices")
+        props = ["x", "y", "z"] + (["nx", "ny", "nz"] if self.normals is not None else [])
+        head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)]
+        head += ["property float %s" % p for p in props]
+        head += ["element face %d" % len(self.faces), "property list uchar int vertex_indices", "end_header"]
+        vrec = np.empty(len(v), dtype=[(p, "<f4") for p in props])
+        for i, p in enumerate("xyz"):
+            vrec[p] = v[:, i]
+        if self.normals is not None:
+            nrm = np.asarray(self.normals, dtype="<f4")
+            for i, p in enumerate(("nx", "ny", "nz")):
+                vrec[p] = nrm[:, i]
+        frec = np.empty(len(self.faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        frec["n"] = 3
+        frec["i"] = np.asarray(self.faces)
+        with open(path, "wb") as f:
+            f.write(("\n".join(head) + "\n").encode("ascii"))
+            f.write(vrec.tobytes())
+            f.write(frec.tobytes())
+
+    def write_stl(self, path):
+        """Binary STL. Facet normals: the normalised mean of the vertex normals when present, else of the face's
+        (v1 - v0) x (v2 - v0)."""
+        v = np.asarray(self.vertices, dtype=np.float32)
+        tri = v[np.asarray(self.faces, dtype=np.int64)].astype(np.float64) if len(self.faces) else np.zeros((0, 3, 3))
+        if self.normals is not None and len(self.faces):
+            nrm = np.asarray(self.normals, dtype=np.float64)[np.asarray(self.faces)].sum(axis=1)
+        else:
+            nrm = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+        length = np.linalg.norm(nrm, axis=1, keepdims=True)
+        nrm = np.divide(nrm, length, out=np.zeros_like(nrm), where=length > 0)
+        rec = np.zeros(len(tri), dtype=[("n", "<f4", (3,)), ("v", "<f4", (3, 3)), ("attr", "<u2")])
+        rec["n"] = nrm
+        rec["v"] = v[np.asarray(self.faces, dtype=np.int64)] if len(self.faces) else np.zeros((0, 3, 3))
+        with open(path, "wb") as f:
+            f.write(b"aegolius_amd isosurface".ljust(80, b" "))
+            f.write(struct.pack("<I", len(rec)))
+            f.write(rec.tobytes())
+
+
+class Contour:
+    """Contour segments: vertices (V, 2) float32, segments (S, 2) int64 with the inside on the left of a -> b."""
+
+    def __init__(self, vertices, segments):
+        self.vertices = vertices
+        self.segments = segments
+
+    def __repr__(self):
+        return "Contour(%d vertices, %d segments)" % (len(self.vertices), len(self.segments))
+
+    def loops(self):
+        """The segments chained into polylines of vertex ids: closed loops first (their first vertex repeated at the
+        end), then open chains (they end on the grid's border), each group in the order of its first segment. Closed
+        loops run counter-clockwise around inside regions and clockwise around holes."""
+        seg = np.asarray(self.segments, dtype=np.int64)
+        nxt = {}
+        has_in = set()
+        for s, (a, b) in enumerate(seg.tolist()):
+            nxt[a] = (b, s)
+            has_in.add(b)
+        used = np.zeros(len(seg), dtype=bool)
+        closed, open_ = [], []
+        for s, (a, _) in enumerate(seg.tolist()):       # open chains start at a vertex nothing leads to
+            if a in has_in or used[s]:
+                continue
+            chain, v = [a], a
+            while v in nxt and not used[nxt[v][1]]:
+                v, k = nxt[v]
+                used[k] = True
+                chain.append(v)
+            open_.append((s, np.asarray(chain, dtype=np.int64)))
+        for s, (a, _) in enumerate(seg.tolist()):
+            if used[s]:
+                continue
+            chain, v = [a], a
+            while not used[nxt[v][1]]:
+                v, k = nxt[v]
+                used[k] = True
+                chain.append(v)
+            closed.append(np.asarray(chain, dtype=np.int64))
+        return closed + [c for _, c in sorted(open_, key=lambda x: x[0])]
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------
+def _tables(axes, dims):
+    """axes: a sequence of 1-D arrays, or a generate_grid array with its grid_axes tag -> list of float32 tables."""
+    tagged = getattr(axes, "grid_axes", None)
+    if tagged is not None:
+        axes = tagged
+    elif isinstance(axes, np.ndarray) and axes.ndim == 2 and axes.shape[0] == 3:
+        raise ValueError("axes: a generate_grid array that is no longer tagged with its axis tables (it was written to or "
+                         "copied); pass the three axis arrays instead")
+    tables = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel(), dtype=np.float32) for a in axes]
+    if dims == 2 and len(tables) == 3:
+        if tables[2].size != 1 or tables[2][0] != 0.0:
+            raise ValueError("contour: three axes are accepted only from a 2-D grid, whose third axis is the single 0.0")
+        tables = tables[:2]
+    if len(tables) != dims:
+        raise ValueError("expected %d axis tables, got %d" % (dims, len(tables)))
+    for a, t in enumerate(tables):
+        if t.size < 2:
+            raise ValueError("axis %d has %d point(s); every axis needs at least 2" % (a, t.size))
+        if not np.all(t[1:] > t[:-1]):
+            raise ValueError("axis %d is not strictly increasing (as float32)" % a)
+    return tables
+
+
+def _level(level):
+    lv = np.float32(level)
+    if np.isnan(lv):
+        raise ValueError("the level is NaN")
+    return float(lv)
+
+
+def _points(field):
+    if isinstance(field, _engine.DeviceField):
+        return field.n
+    return int(np.asarray(field).size)
+
+
+def _extract(field, tables, level, timings=None):
+    dims = len(tables)
+    shape = tuple(t.size for t in tables)
+    n = int(np.prod(shape))
+    if _points(field) != n:
+        raise ValueError("the field has %d values; the axes span %s = %d points" % (_points(field), "x".join(map(str, shape)), n))
+    lv = _level(level)
+    own = None
+    if isinstance(field, _engine.DeviceField):
+        dev = field
+        dev._live()
+    else:
+        dev = own = _engine.DeviceField.from_host(np.asarray(field, dtype=np.float32).ravel(), _device())
+    L = _engine.lib()
+    c = ctypes
+    nv, nf = _engine._i64(0), _engine._i64(0)
+    bufs = []
+
+    def alloc(nbytes):
+        p = L.sdfk_malloc(max(int(nbytes), 1))
+        if not p:
+            raise _engine.SdfkError("mesh: out of device memory (%d bytes)" % nbytes)
+        bufs.append(p)
+        return c.c_void_p(p)
+
+    ev = []
+
+    def mark():
+        if timings is not None:
+            e = _engine.Event()
+            e.record()
+            ev.append(e)
+
+    try:
+        mark()
+        if dims == 3:
+            d_scratch = alloc(L.sdfk_field_isosurface_scratch(*shape))
+            _engine.check(L.sdfk_field_isosurface(c.c_void_p(dev.ptr), _engine._ptr(tables[0]), shape[0], _engine._ptr(tables[1]),
+                                                  shape[1], _engine._ptr(tables[2]), shape[2], lv, c.byref(nv), c.byref(nf),
+                                                  d_scratch, None), "sdfk_field_isosurface")
+        else:
+            d_scratch = alloc(L.sdfk_field_contour2d_scratch(*shape))
+            _engine.check(L.sdfk_field_contour2d(c.c_void_p(dev.ptr), _engine._ptr(tables[0]), shape[0], _engine._ptr(tables[1]),
+                                                 shape[1], lv, c.byref(nv), c.byref(nf), d_scratch, None), "sdfk_field_contour2d")
+        mark()
+        V, F = nv.value, nf.value
+        wide = V > 0x7fffffff
+        d_v = alloc(V * dims * 4)
+        d_f = alloc(F * dims * (8 if wide else 4))
+        if dims == 3:
+            _engine.check(L.sdfk_field_isosurface_finish(c.c_void_p(dev.ptr), shape[0], shape[1], shape[2], lv, V, F, d_v, V, d_f, F,
+                                                         8 if wide else 4, d_scratch, None), "sdfk_field_isosurface_finish")
+        else:
+            _engine.check(L.sdfk_field_contour2d_finish(c.c_void_p(dev.ptr), shape[0], shape[1], lv, V, F, d_v, V, d_f, F,
+                                                        8 if wide else 4, d_scratch, None), "sdfk_field_contour2d_finish")
+        mark()
+        verts = np.empty((V, dims), dtype=np.float32)
+        faces = np.empty((F, dims), dtype=np.int64 if wide else np.int32)
+        if V:
+            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(verts), d_v, verts.nbytes), "sdfk_memcpy_d2h")
+        if F:
+            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(faces), d_f, faces.nbytes), "sdfk_memcpy_d2h")
+        mark()
+        if timings is not None:
+            for name, a, b in zip(("count", "emit", "copy"), ev, ev[1:]):
+                timings[name] = a.elapsed_ms(b)
+        return verts, faces.astype(np.int64, copy=False)
+    finally:
+        for p in bufs:
+            L.sdfk_free(c.c_void_p(p))
+        if own is not None:
+            own.free()
+
+
+def _device():
+    from ._eval import config
+    return config.device
+
+
+# ---- public interface -------------------------------------------------------------------------------------------------------
+def isosurface(field, axes, level=0.0, timings=None):
+    """Triangle mesh of {f = level} of a 3-D field. `field`: a DeviceField or a host array of nx ny nz values in C order
+    (generate_grid's layout); `axes`: three strictly increasing 1-D arrays (lengths nx, ny, nz, each >= 2, uniform or
+    not) or a generate_grid array. `timings`: a dict that receives device-event milliseconds of count / emit / copy."""
+    tables = _tables(axes, 3)
+    verts, faces = _extract(field, tables, level, timings)
+    return Mesh(verts, faces)
+
+
+def contour(field, axes, level=0.0, timings=None):
+    """Segments of {f = level} of a 2-D field of nx ny values: `axes` is (x, y), or the three axes / the array of a 2-D
+    generate_grid (third axis the single 0.0). The shape is taken from the axes."""
+    tables = _tables(axes, 2)
+    verts, segs = _extract(field, tables, level, timings)
+    return Contour(verts, segs)
+
+
+def from_geometry(geometry, size, resolution, level=0.0):
+    """generate_grid(size, resolution), create_resident, then isosurface (3 sizes) or contour (2 sizes); the field is
+    freed afterwards."""
+    from .cores import generate_grid
+    dims = len(size)
+    if dims not in (2, 3):
+        raise ValueError("from_geometry: size has 2 (contour) or 3 (isosurface) entries")
+    co, _ = generate_grid(size, resolution)
+    axes = getattr(co, "grid_axes", None)
+    if axes is None:
+        from .cores.helper_functions import grid_axes
+        axes, _ = grid_axes(size, resolution)
+    dev = geometry.create_resident(co)
+    try:
+        return isosurface(dev, axes, level) if dims == 3 else contour(dev, axes, level)
+    finally:
+        dev.free()

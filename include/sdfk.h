@@ -442,6 +442,29 @@ int sdfk_points_fill(unsigned char* d_grid, int64_t rx, int64_t ry, int64_t rz, 
                      void* stream);
 int sdfk_points_widen(const unsigned char* d_grid, int64_t n, int kind, void* d_out, void* stream);
 
+/* ---- isosurface and contour extraction (aegolius_amd.mesh; csrc/sdfk_mesh.inc) ----------------------------------------
+ * d_field: the (n0, n1, n2) field in C order (2-D: (n0, n1)), DEVICE, 16-byte aligned. ax0 .. ax2: HOST tables of the
+ * axis coordinates (as sdfk_eval_grid_select takes them), each strictly increasing with at least 2 points. A point is
+ * inside if field <= level (NaN outside; a NaN level is refused). One vertex per grid edge whose ends differ, numbered by
+ * (owning lower point, axis); triangles (segments) by (cell, case-table order), counter-clockwise seen from outside
+ * (segments: inside on the left). The exact definition is that of aegolius_amd/mesh.py.
+ * Two steps, as sdfk_field_select: the counting call reads the field once, leaves its state in d_scratch (*_scratch bytes,
+ * 256-byte aligned device memory) and returns the counts; *_finish writes the vertices (float32, 3 or 2 per vertex) and
+ * the faces (3 or 2 vertex ids per entry, face_bytes 4 = int32, needs fewer than 2^31 vertices, or 8 = int64) up to the
+ * given capacities, which must hold the counts. finish takes the same field, shape and level. */
+size_t sdfk_field_isosurface_scratch(int64_t n0, int64_t n1, int64_t n2);
+int sdfk_field_isosurface(const float* d_field, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                          int64_t n2, float level, int64_t* n_vertices, int64_t* n_faces, void* d_scratch, void* stream);
+int sdfk_field_isosurface_finish(const float* d_field, int64_t n0, int64_t n1, int64_t n2, float level, int64_t n_vertices,
+                                 int64_t n_faces, float* d_vertices, int64_t vertex_capacity, void* d_faces,
+                                 int64_t face_capacity, int face_bytes, void* d_scratch, void* stream);
+size_t sdfk_field_contour2d_scratch(int64_t n0, int64_t n1);
+int sdfk_field_contour2d(const float* d_field, const float* ax0, int64_t n0, const float* ax1, int64_t n1, float level,
+                         int64_t* n_vertices, int64_t* n_segments, void* d_scratch, void* stream);
+int sdfk_field_contour2d_finish(const float* d_field, int64_t n0, int64_t n1, float level, int64_t n_vertices,
+                                int64_t n_segments, float* d_vertices, int64_t vertex_capacity, void* d_segments,
+                                int64_t segment_capacity, int segment_bytes, void* d_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
