@@ -118,6 +118,16 @@ SIGNATURES = {
     "sdfk_field_contour2d_scratch": (_sz, [_i64, _i64]),
     "sdfk_field_contour2d": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64), _vp, _vp]),
     "sdfk_field_contour2d_finish": (_int, [_vp, _i64, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp]),
+    "sdfk_eval_grid_isosurface_scratch": (_sz, [_i64, _i64, _i64]),
+    "sdfk_eval_grid_isosurface": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64),
+                                         _vp, _vp, _int]),
+    "sdfk_eval_grid_isosurface_finish": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp,
+                                                _i64, _int, _vp, _vp, _int]),
+    "sdfk_eval_grid_contour2d_scratch": (_sz, [_i64, _i64]),
+    "sdfk_eval_grid_contour2d": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64), _vp, _vp,
+                                        _int]),
+    "sdfk_eval_grid_contour2d_finish": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int,
+                                               _vp, _vp, _int]),
 }
 
 
@@ -351,6 +361,75 @@ class Program:
                                               mode), "sdfk_eval_grid_select")
         grow = ax[2].size if ax[2].size > 1 else ax[1].size
         return self._select(count, first, device, row_len=grow if start % grow == 0 and count % grow == 0 else 0, mode=mode)
+
+    def mesh_grid(self, axes, level, device=0, mode=MODE_AUTO, timings=None):
+        """Isosurface (three axis tables) or contour (two) of {f = level} on the grid the tables span, WITHOUT a field:
+        the evaluation kernels write one inside bit per point, the mesh is counted from the bits, and the program is
+        evaluated again at the two ends of every crossing edge (sdfk_eval_grid_isosurface / _contour2d and their
+        _finish). The tables must be strictly increasing float32 arrays and `level` not NaN (aegolius_amd.mesh checks
+        both). -> (vertices (V, D) float32, faces (F, D) int32, or int64 from 2^31 vertices on). `timings`: a dict that
+        receives device-event milliseconds of count (evaluation to bits, count, scan) / emit / copy."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+        dims = len(ax)
+        if dims not in (2, 3):
+            raise ValueError("mesh_grid: two or three axis tables")
+        shape = [a.size for a in ax]
+        tab = []
+        for a in ax:
+            tab += [_ptr(a), a.size]
+        lv = _c.c_float(level)
+        nv, nf = _i64(0), _i64(0)
+        bufs, ev = [], []
+
+        def alloc(nbytes):
+            p = L.sdfk_malloc(max(int(nbytes), 1))
+            if not p:
+                raise SdfkError("mesh: out of device memory (%d bytes)" % nbytes)
+            bufs.append(p)
+            return _vp(p)
+
+        def mark():
+            if timings is not None:
+                e = Event()
+                e.record()
+                ev.append(e)
+
+        try:
+            mark()
+            if dims == 3:
+                d_scratch = alloc(L.sdfk_eval_grid_isosurface_scratch(*shape))
+                check(L.sdfk_eval_grid_isosurface(self._h, *tab, lv, ctypes.byref(nv), ctypes.byref(nf), d_scratch, None, mode),
+                      "sdfk_eval_grid_isosurface")
+            else:
+                d_scratch = alloc(L.sdfk_eval_grid_contour2d_scratch(*shape))
+                check(L.sdfk_eval_grid_contour2d(self._h, *tab, lv, ctypes.byref(nv), ctypes.byref(nf), d_scratch, None, mode),
+                      "sdfk_eval_grid_contour2d")
+            mark()
+            V, F = nv.value, nf.value
+            wide = V > 0x7fffffff
+            d_v = alloc(V * dims * 4)
+            d_f = alloc(F * dims * (8 if wide else 4))
+            fin = L.sdfk_eval_grid_isosurface_finish if dims == 3 else L.sdfk_eval_grid_contour2d_finish
+            check(fin(self._h, *tab, lv, V, F, d_v, V, d_f, F, 8 if wide else 4, d_scratch, None, mode),
+                  "sdfk_eval_grid_isosurface_finish" if dims == 3 else "sdfk_eval_grid_contour2d_finish")
+            mark()
+            verts = np.empty((V, dims), dtype=np.float32)
+            faces = np.empty((F, dims), dtype=np.int64 if wide else np.int32)
+            if V:
+                check(L.sdfk_memcpy_d2h(_ptr(verts), d_v, verts.nbytes), "sdfk_memcpy_d2h")
+            if F:
+                check(L.sdfk_memcpy_d2h(_ptr(faces), d_f, faces.nbytes), "sdfk_memcpy_d2h")
+            mark()
+            if timings is not None:
+                for name, a, b in zip(("count", "emit", "copy"), ev, ev[1:]):
+                    timings[name] = a.elapsed_ms(b)
+            return verts, faces
+        finally:
+            for p in bufs:
+                L.sdfk_free(_vp(p))
 
     def select_host(self, co, threshold=0.0, device=0, mode=MODE_AUTO):
         """The same for a (3, N) host array (uploaded once as float32; the row-length hint is detected like create())."""

@@ -1,11 +1,13 @@
 """Isosurface meshes and 2-D contours of scalar fields, extracted on the GPU (kernels: csrc/sdfk_mesh.inc).
 
     from aegolius_amd import mesh
-    m = mesh.from_geometry(geometry, (2, 2, 2), (257, 257, 257))      # or mesh.isosurface(device_field, co)
+    m = mesh.from_geometry(geometry, (2, 2, 2), (257, 257, 257))      # or mesh.isosurface(geometry or device_field, co)
     m.compute_normals(geometry)
     m.write_ply("part.ply")
 
-The field stays in HBM (a DeviceField, or a host array uploaded once); only the mesh crosses PCIe.
+The field stays in HBM (a DeviceField, or a host array uploaded once); only the mesh crosses PCIe. A geometry is meshed
+without a field at all: its evaluation writes one inside bit per grid point, and it is evaluated again only at the two
+ends of every crossing edge ("geometry path") — the same output, bit for bit, as meshing its field.
 
 Output definition (the kernels and tests/mesh_reference.py implement exactly this):
   * A grid point is inside if f <= level. NaN is outside.
@@ -266,38 +268,91 @@ def _device():
     return config.device
 
 
+# ---- geometries -------------------------------------------------------------------------------------------------------------
+def _is_geometry(obj):
+    from .cores.geom import GenericGeometry
+    return isinstance(obj, GenericGeometry)
+
+
+def _grid_array(axes):
+    """The tagged (3, N) grid of the axis tables (what generate_grid returns), for trees evaluated to a field first."""
+    from .cores.helper_functions import GridCoords
+    ax = [np.asarray(a, dtype=np.float64).ravel() for a in axes]
+    ax += [np.zeros(1)] * (3 - len(ax))
+    n = [a.size for a in ax]
+    co = GridCoords((3, n[0] * n[1] * n[2]), dtype=np.float64)
+    shaped = np.asarray(co).reshape(3, *n)
+    shaped[0] = ax[0][:, None, None]
+    shaped[1] = ax[1][None, :, None]
+    shaped[2] = ax[2][None, None, :]
+    co._grid_axes = ax
+    co.setflags(write=False)
+    return co
+
+
+def _extract_geometry(geometry, tables, level, timings, grid):
+    """Mesh of a geometry on the grid of `tables`. A tree that lowers to one program is evaluated to inside bits and at
+    the crossing edges' ends only (_engine.Program.mesh_grid); a staged tree (NeedsStage) is evaluated to a resident
+    field on the grid `grid()` returns, which is then meshed — the rule of _eval.select_geometry."""
+    from ._eval import config, program_for
+    from ._lower import NeedsStage, lower_geometry
+    lv = _level(level)
+    geometry._sdf = geometry.modified_object                   # (as create() does)
+    try:
+        lowered = lower_geometry(geometry)
+    except NeedsStage:
+        dev = geometry.create_resident(grid())
+        try:
+            return _extract(dev, tables, lv, timings)
+        finally:
+            dev.free()
+    verts, faces = program_for(lowered).mesh_grid(tables, lv, device=config.device, mode=config.mode, timings=timings)
+    return verts, faces.astype(np.int64, copy=False)
+
+
+def _grid_of(axes):
+    return lambda: axes if getattr(axes, "grid_axes", None) is not None else _grid_array(axes)
+
+
 # ---- public interface -------------------------------------------------------------------------------------------------------
 def isosurface(field, axes, level=0.0, timings=None):
-    """Triangle mesh of {f = level} of a 3-D field. `field`: a DeviceField or a host array of nx ny nz values in C order
-    (generate_grid's layout); `axes`: three strictly increasing 1-D arrays (lengths nx, ny, nz, each >= 2, uniform or
-    not) or a generate_grid array. `timings`: a dict that receives device-event milliseconds of count / emit / copy."""
+    """Triangle mesh of {f = level} of a 3-D field. `field`: a DeviceField, a host array of nx ny nz values in C order
+    (generate_grid's layout), or a geometry (GenericGeometry: any tree create() evaluates), meshed without a field or a
+    coordinate array; `axes`: three strictly increasing 1-D arrays (lengths nx, ny, nz, each >= 2, uniform or not) or a
+    generate_grid array. `timings`: a dict that receives device-event milliseconds of count / emit / copy (a geometry's
+    evaluation to inside bits is part of count)."""
     tables = _tables(axes, 3)
-    verts, faces = _extract(field, tables, level, timings)
+    if _is_geometry(field):
+        verts, faces = _extract_geometry(field, tables, level, timings, _grid_of(axes))
+    else:
+        verts, faces = _extract(field, tables, level, timings)
     return Mesh(verts, faces)
 
 
 def contour(field, axes, level=0.0, timings=None):
-    """Segments of {f = level} of a 2-D field of nx ny values: `axes` is (x, y), or the three axes / the array of a 2-D
-    generate_grid (third axis the single 0.0). The shape is taken from the axes."""
+    """Segments of {f = level} of a 2-D field of nx ny values, or of a geometry on that grid: `axes` is (x, y), or the
+    three axes / the array of a 2-D generate_grid (third axis the single 0.0). The shape is taken from the axes."""
     tables = _tables(axes, 2)
-    verts, segs = _extract(field, tables, level, timings)
+    if _is_geometry(field):
+        verts, segs = _extract_geometry(field, tables, level, timings, _grid_of(axes))
+    else:
+        verts, segs = _extract(field, tables, level, timings)
     return Contour(verts, segs)
 
 
 def from_geometry(geometry, size, resolution, level=0.0):
-    """generate_grid(size, resolution), create_resident, then isosurface (3 sizes) or contour (2 sizes); the field is
-    freed afterwards."""
-    from .cores import generate_grid
+    """isosurface (3 sizes) or contour (2 sizes) of `geometry` on the grid generate_grid(size, resolution) spans, from
+    its axis tables (grid_axes): neither the coordinate array nor a field is made, except for staged trees, which are
+    evaluated to a field on generate_grid's array first."""
+    from .cores.helper_functions import grid_axes
     dims = len(size)
     if dims not in (2, 3):
         raise ValueError("from_geometry: size has 2 (contour) or 3 (isosurface) entries")
-    co, _ = generate_grid(size, resolution)
-    axes = getattr(co, "grid_axes", None)
-    if axes is None:
-        from .cores.helper_functions import grid_axes
-        axes, _ = grid_axes(size, resolution)
-    dev = geometry.create_resident(co)
-    try:
-        return isosurface(dev, axes, level) if dims == 3 else contour(dev, axes, level)
-    finally:
-        dev.free()
+    axes, _ = grid_axes(size, resolution)
+    tables = _tables(axes, dims)
+
+    def grid():
+        from .cores import generate_grid
+        return generate_grid(size, resolution)[0]
+    verts, faces = _extract_geometry(geometry, tables, level, None, grid)
+    return Mesh(verts, faces) if dims == 3 else Contour(verts, faces)

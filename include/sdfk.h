@@ -464,6 +464,28 @@ int sdfk_field_contour2d(const float* d_field, const float* ax0, int64_t n0, con
 int sdfk_field_contour2d_finish(const float* d_field, int64_t n0, int64_t n1, float level, int64_t n_vertices,
                                 int64_t n_segments, float* d_vertices, int64_t vertex_capacity, void* d_segments,
                                 int64_t segment_capacity, int segment_bytes, void* d_scratch, void* stream);
+/* The same meshes of a PROGRAM on the grid of the axis tables, without a field or a coordinate array: the evaluation
+ * kernels write one inside bit per point (their flag builds, as sdfk_eval_grid_select), and the finishing call evaluates
+ * the program again only at the two ends of every crossing edge. Output identical to evaluating the grid to a field
+ * (sdfk_eval_grid) and calling sdfk_field_isosurface / _contour2d on it. Same two steps and output buffers; d_scratch:
+ * *_scratch bytes (at most 1 byte per grid point plus O(n0 + n1 + n2 + n / 8192)), 256-byte aligned. The finishing call
+ * takes the tables, level and mode of the counting call; while it runs it allocates 32 bytes per vertex for the edge
+ * ends and their values. Programs with auxiliary fields (staged) are refused: evaluate them to a field first. */
+size_t sdfk_eval_grid_isosurface_scratch(int64_t n0, int64_t n1, int64_t n2);
+int sdfk_eval_grid_isosurface(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                              int64_t n2, float level, int64_t* n_vertices, int64_t* n_faces, void* d_scratch, void* stream,
+                              int mode);
+int sdfk_eval_grid_isosurface_finish(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
+                                     const float* ax2, int64_t n2, float level, int64_t n_vertices, int64_t n_faces,
+                                     float* d_vertices, int64_t vertex_capacity, void* d_faces, int64_t face_capacity,
+                                     int face_bytes, void* d_scratch, void* stream, int mode);
+size_t sdfk_eval_grid_contour2d_scratch(int64_t n0, int64_t n1);
+int sdfk_eval_grid_contour2d(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, float level,
+                             int64_t* n_vertices, int64_t* n_segments, void* d_scratch, void* stream, int mode);
+int sdfk_eval_grid_contour2d_finish(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, float level,
+                                    int64_t n_vertices, int64_t n_segments, float* d_vertices, int64_t vertex_capacity,
+                                    void* d_segments, int64_t segment_capacity, int segment_bytes, void* d_scratch,
+                                    void* stream, int mode);
 
 #ifdef __cplusplus
 }
