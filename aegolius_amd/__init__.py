@@ -12,5 +12,6 @@ from ._eval import config  # noqa: F401
 from ._engine import DeviceField, DeviceVectorField  # noqa: F401
 from . import cores  # noqa: F401
 from . import mesh  # noqa: F401
+from . import render  # noqa: F401
 
 __version__ = "0.1.0"

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libsdfk.so")
 
 MODE_AUTO, MODE_INTERPRET, MODE_SPECIALIZED, MODE_NOCULL = 0, 1, 2, 3
 (FLAVOUR_PLAIN_ARRAY, FLAVOUR_PLAIN_GRID, FLAVOUR_TILE_ARRAY, FLAVOUR_TILE_GRID, FLAVOUR_TILE_MASK, FLAVOUR_ROWS_ARRAY,
- FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID) = range(10)
+ FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID, FLAVOUR_RAYS) = range(11)
 FLAVOUR_FLAGS = 0x100      # OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (fused selection)
 FLAVOUR_XY = 0x200         # OR-ed onto PLAIN_ARRAY / ROWS2D_ARRAY: the build for two-row coordinates (z = 0 by contract)
 
@@ -128,6 +128,11 @@ SIGNATURES = {
                                         _int]),
     "sdfk_eval_grid_contour2d_finish": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int,
                                                _vp, _vp, _int]),
+    "sdfk_program_rays_check": (_int, [_vp, _c.POINTER(_int)]),
+    "sdfk_trace_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
+                                      _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
+    "sdfk_trace_camera_device": (_int, [_vp, _vp, _int, _int, _int, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
+                                        _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
 }
 
 

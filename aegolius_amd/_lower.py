@@ -34,7 +34,7 @@ class LoweringError(Exception):
 
 class LoweredProgram:
     __slots__ = ("code", "params", "tables", "result_reg", "n_creg", "n_vreg", "cull_sites", "cull_k", "stage_params",
-                 "params64")
+                 "params64", "lipschitz")
 
     def __init__(self, code, params, tables, result_reg, n_creg, n_vreg, cull_sites=None, cull_k=None):
         self.code, self.params, self.tables = code, params, tables
@@ -44,6 +44,9 @@ class LoweredProgram:
         self.cull_k = np.zeros(0, dtype=np.float32) if cull_k is None else cull_k
         self.stage_params = ()     # stage programs: the geometry parameters the staged operator's closure is called with
         self.params64 = None       # the parameter table before its rounding to fp32 (set by Lowerer.finish)
+        # Lipschitz bound of the result register with respect to the root point (_lipschitz.py; set by Lowerer.finish,
+        # inf where no bound is known): the safe step divisor of sphere tracing (aegolius_amd.render). Not part of key().
+        self.lipschitz = _lip.INF
 
     def key(self):
         return (self.code.tobytes(), self.params.tobytes(), self.tables.tobytes(), self.result_reg,
@@ -282,6 +285,7 @@ class Lowerer:
                              np.asarray([r[:5] for r in sites], dtype=np.uint32).reshape(-1, 5),
                              np.asarray([r[5] for r in sites], dtype=np.float32))
         low.params64 = np.asarray(self.params, dtype=np.float64)
+        low.lipschitz = float(self.lip_v.get(vreg, _lip.INF))
         return low
 
     # ---- coordinate helpers ----

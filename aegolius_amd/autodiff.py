@@ -67,7 +67,8 @@ def _describe(expr):
 
 
 class _TracingLowerer(Lowerer):
-    """A Lowerer that remembers which cores object emitted each instruction (for the error messages)."""
+    """A Lowerer that remembers which cores object emitted each instruction (for the error messages).
+    Also the base of aegolius_amd.render's lowerer (`origin`, `emit`): keep both when this class changes."""
 
     def __init__(self, shortcuts):
         Lowerer.__init__(self, shortcuts)
@@ -226,7 +227,8 @@ def _stride(n):
 
 class _Coords:
     """(3, N) coordinates on the device: a DeviceVectorField, a generate_grid array (filled on the device from its axis
-    tables) or a host array (uploaded as fp32, as create() does)."""
+    tables) or a host array (uploaded as fp32, as create() does). aegolius_amd.render uploads its rays through this class
+    too (`ptr`, `stride`, `n`, `free()`)."""
 
     def __init__(self, co):
         L = _engine.lib()

@@ -89,6 +89,31 @@ extern "C" __global__ __launch_bounds__(SDFK_BLOCK) void sdfk_spec_g1(
 }
 )SDFKW";
 
+// Sphere tracing (SDFK_FL_RAYS): the marching loop of sdfk_raydev.h around the generated body. Array rays and camera rays
+// in one translation unit; the same text as the interpreter ray kernel (sdfk_rays.inc) but for the evaluator.
+static const char kRays[] = R"SDFKW(
+struct SdfkSpecField {
+    const float* __restrict__ PRM;
+    const float* __restrict__ TAB;
+    __device__ __forceinline__ float operator()(V3 p) const { return sdfk_point<float>(p, PRM, TAB, nullptr, 0); }
+};
+extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_rays(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkRaysArray src, sdfk_rayopts opts,
+    float* __restrict__ out_t, unsigned char* __restrict__ out_status, int* __restrict__ out_steps,
+    float* __restrict__ out_n, long long nstride) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride);
+}
+extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_raycam(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, sdfk_camera cam, sdfk_rayopts opts,
+    float* __restrict__ out_t, unsigned char* __restrict__ out_status, int* __restrict__ out_steps,
+    float* __restrict__ out_n, long long nstride) {
+    const SdfkSpecField field = {PRM, TAB};
+    const SdfkRaysCamera src = {cam};
+    sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride);
+}
+)SDFKW";
+
 // Pieces shared by the two culling kernel families.
 static const char kWaveHelpers[] = R"SDFKH(
 #ifndef SDFK_TWAVES
@@ -2485,6 +2510,26 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
     g.s += "\n";
     g.s += kEmbeddedAccess;
     char buf[64];
+    if (flavour == SDFK_FL_RAYS) {
+        // Sphere tracing: the plain body, one ray per lane (scalar T: lanes diverge per ray, and two rays per lane would
+        // double every wave's tail), inside the marching loop of sdfk_raydev.h. A long hard union that the field kernels
+        // run table-driven ("chain mode") keeps its table-driven plain body — every member at every step, no candidate
+        // lists: there is no culling structure for rays — which builds in a second whatever the number of members.
+        if (chain_analyse(g, result_reg, sites_all)) {
+            g.emit_chain_common();
+        } else {
+            g.s += "\ntemplate <typename T> static __device__ __forceinline__ T sdfk_point(V3T<T> C_0, "
+                   "const float* __restrict__ PRM, const float* __restrict__ TAB, const float* __restrict__ AUX, "
+                   "long long AUXS) {\n";
+            g.declare("V3T<T>", "T", false);
+            for (size_t i = 0; i < n_instr; ++i) g.instr(i, "    ");
+            snprintf(buf, sizeof buf, "    return V_%d;\n}\n", result_reg);
+            g.s += buf;
+        }
+        g.s += kEmbeddedRaydev;
+        g.s += kRays;
+        return g.s;
+    }
     if (chain_analyse(g, result_reg, sites_all)) {
         // chain mode: table-driven plain kernels and row-block kernels (no line-brick flavour)
         const bool flat2 = flavour == SDFK_FL_ROWS2D_ARRAY || flavour == SDFK_FL_ROWS2D_GRID;

@@ -41,8 +41,9 @@ enum sdfk_flavour {
     SDFK_FL_ROWS_MASK,         // sdfk_spec_rmask (test aid)
     SDFK_FL_ROWS2D_ARRAY,      // sdfk_spec_r  built for flat grids (rows along y, z = 0: SDFK_FLAT)
     SDFK_FL_ROWS2D_GRID,       // sdfk_spec_rg built for flat grids
+    SDFK_FL_RAYS,              // sdfk_spec_rays + sdfk_spec_raycam: sphere tracing around sdfk_point<float> (sdfk_raydev.h)
     SDFK_FL_COUNT,
-    SDFK_FL_ALL = SDFK_FL_COUNT   // everything in one unit (sdfk_program_source, developer tools)
+    SDFK_FL_ALL = SDFK_FL_COUNT   // every evaluation flavour in one unit (sdfk_program_source, developer tools)
 };
 // sites: what the mask kernels use (at most 64); sites_all (optional): every site of the program — a long n-ary
 // min / max chain whose children read nothing but the input point is generated TABLE-DRIVEN from them ("chain mode":

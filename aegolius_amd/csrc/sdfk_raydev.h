@@ -1,0 +1,159 @@
+// sdfk_raydev.h — sphere tracing of one program: the marching loop, the ray sources and the stencil normals. Shared
+// (like sdfk_access.h) by the interpreter ray kernel (sdfk_rays.inc) and, as embedded text, by the hiprtc-specialised
+// one (SDFK_FL_RAYS), so that the marching arithmetic is ONE piece of text: both kernels give the same bits.
+//
+// The marching rule (aegolius_amd/render.py states it for users; tests/render_reference.py is its float64 copy):
+//     t = t_min
+//     repeat at most max_steps times:
+//         f   = field(o + t d)                     fp32: fmaf(t, d, o) per component
+//         thr = max(eps, cone t)
+//         if f <= thr: hit, stop                   (steps = advances made so far: 0 for a ray that starts on the solid)
+//         t   = fmaf(f, 1 / L, t)                  1 / L rounded once on the host; steps += 1
+//         if t > t_max: miss, stop
+//     otherwise: step limit
+// One ray per lane. The loop runs while any lane of the wave still marches: the trip count is wave-uniform, so the
+// evaluator's code words stay scalar loads; lanes that have finished evaluate along and are masked out of every update.
+#ifndef SDFK_RAYDEV_H
+#define SDFK_RAYDEV_H
+
+#define SDFK_RAY_BLOCK 256
+#define SDFK_RAY_MISS 0u
+#define SDFK_RAY_HIT 1u
+#define SDFK_RAY_LIMIT 2u
+
+struct sdfk_rayopts {
+    float t_min, t_max, eps, cone, inv_lip;
+    int max_steps;
+};
+// Camera record. Pixel (ix, iy), iy = 0 the TOP row, a = (2 ix + 1) / W - 1, b = 1 - (2 iy + 1) / H:
+//   perspective : o = eye,                 d = (fwd + a du + b dv) / |fwd + a du + b dv|
+//   orthographic: o = eye + a du + b dv,   d = fwd
+// fwd is a unit vector, du / dv the right / up unit vectors scaled by half the extent of the image plane (at distance
+// 1 for the perspective camera).
+struct sdfk_camera {
+    float eye[3], fwd[3], du[3], dv[3];
+    float inv_w, inv_h;        // 1 / W, 1 / H rounded to fp32 on the host
+    int width, height, ortho;
+};
+
+struct SdfkRaysArray {      // two (3, n) arrays, rows strided like d_co everywhere else; ray i on lane i of the launch
+    const float* __restrict__ o;
+    long long ostride;
+    const float* __restrict__ d;
+    long long dstride;
+    long long n;
+};
+struct SdfkRaysCamera {     // rays generated from the record; every wave owns one tile of 8 x 8 pixels
+    sdfk_camera cam;
+};
+
+// -> is there a ray on this lane; its origin, direction and the index its results are stored at
+static __device__ __forceinline__ bool sdfk_ray_load(const SdfkRaysArray& s, V3& o, V3& d, long long& at) {
+    at = (long long)sdfk_bx() * SDFK_RAY_BLOCK + sdfk_tx();
+    o = {0.0f, 0.0f, 0.0f};
+    d = {0.0f, 0.0f, 0.0f};
+    if (at >= s.n) return false;
+    o = {s.o[at], s.o[s.ostride + at], s.o[2 * s.ostride + at]};
+    d = {s.d[at], s.d[s.dstride + at], s.d[2 * s.dstride + at]};
+    return true;
+}
+static __device__ __forceinline__ bool sdfk_ray_load(const SdfkRaysCamera& s, V3& o, V3& d, long long& at) {
+    const sdfk_camera& c = s.cam;
+    const unsigned tiles_x = ((unsigned)c.width + 7u) >> 3;
+    const unsigned tile = sdfk_bx() * (SDFK_RAY_BLOCK / 64) + (sdfk_tx() >> 6);   // wave-uniform
+    const unsigned ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const unsigned lane = sdfk_tx() & 63u;
+    const unsigned ix = tx * 8u + (lane & 7u), iy = ty * 8u + (lane >> 3);
+    at = (long long)iy * c.width + ix;
+    o = {0.0f, 0.0f, 0.0f};
+    d = {0.0f, 0.0f, 0.0f};
+    if (ix >= (unsigned)c.width || iy >= (unsigned)c.height) return false;
+    const float a = fmaf((float)(2u * ix + 1u), c.inv_w, -1.0f);
+    const float b = fmaf(-(float)(2u * iy + 1u), c.inv_h, 1.0f);
+    const V3 q = {fmaf(b, c.dv[0], a * c.du[0]), fmaf(b, c.dv[1], a * c.du[1]), fmaf(b, c.dv[2], a * c.du[2])};
+    if (c.ortho) {
+        o = {c.eye[0] + q.x, c.eye[1] + q.y, c.eye[2] + q.z};
+        d = {c.fwd[0], c.fwd[1], c.fwd[2]};
+    } else {
+        const V3 w = {c.fwd[0] + q.x, c.fwd[1] + q.y, c.fwd[2] + q.z};
+        const float inv = 1.0f / sqrtf(fmaf(w.z, w.z, fmaf(w.y, w.y, w.x * w.x)));
+        o = {c.eye[0], c.eye[1], c.eye[2]};
+        d = {w.x * inv, w.y * inv, w.z * inv};
+    }
+    return true;
+}
+
+// Width of the normal stencil at a hit: the hit threshold there, floored at 2^-16 max(|x|, |y|, |z|) — 128 fp32
+// spacings of the largest coordinate, so that the four stencil points are distinct numbers and the difference of their
+// field values keeps about 7 bits (aegolius_amd.render.stencil_width is the same arithmetic on the host).
+static __device__ __forceinline__ float sdfk_ray_stencil_width(float thr, V3 p) {
+    const float m = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z));
+    return fmaxf(thr, 1.52587890625e-05f * m);
+}
+
+// FIELD: float operator()(V3) const — the program at one point (interpreter switch or the generated sdfk_point<float>)
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_trace(const SRC& src, const FIELD& field, const sdfk_rayopts R,
+                                                  float* __restrict__ out_t, unsigned char* __restrict__ out_status,
+                                                  int* __restrict__ out_steps, float* __restrict__ out_n,
+                                                  long long nstride) {
+    V3 o, d;
+    long long at;
+    const bool live = sdfk_ray_load(src, o, d, at);
+    float t = R.t_min, thr = R.eps;
+    unsigned status = SDFK_RAY_LIMIT;
+    int steps = 0;
+    bool marching = live;
+    for (int it = 0; it < R.max_steps; ++it) {
+        if (!__any(marching)) break;
+        const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
+        const float f = field(p);
+        if (marching) {
+            thr = fmaxf(R.eps, R.cone * t);
+            if (f <= thr) {
+                status = SDFK_RAY_HIT;
+                marching = false;
+            } else {
+                t = fmaf(f, R.inv_lip, t);
+                ++steps;
+                if (t > R.t_max) {
+                    status = SDFK_RAY_MISS;
+                    marching = false;
+                }
+            }
+        }
+    }
+    if (live) {
+        out_t[at] = t;
+        out_status[at] = (unsigned char)status;
+        out_steps[at] = steps;
+    }
+    if (!out_n) return;                                       // wave-uniform (a kernel argument)
+    // four-point tetrahedron difference at the hit: g = sum_i k_i f(p + h k_i), k = (+--), (--+), (-+-), (+++), summed
+    // in that order; g / 4h is the gradient, the normal is g / |g|. Lanes that did not hit store the zero vector.
+    const bool hit = live && status == SDFK_RAY_HIT;
+    V3 nrm = {0.0f, 0.0f, 0.0f};
+    if (__any(hit)) {
+        const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
+        const float h = sdfk_ray_stencil_width(thr, p);
+        V3 g = {0.0f, 0.0f, 0.0f};
+        _Pragma("unroll 1") for (int k = 0; k < 4; ++k) {       // (one call site: the body is inlined once, not four times)
+            const float kx = (k == 0 || k == 3) ? 1.0f : -1.0f, ky = (k >= 2) ? 1.0f : -1.0f,
+                        kz = (k == 1 || k == 3) ? 1.0f : -1.0f;
+            const float f = field(V3{fmaf(kx, h, p.x), fmaf(ky, h, p.y), fmaf(kz, h, p.z)});
+            g = {g.x + kx * f, g.y + ky * f, g.z + kz * f};
+        }
+        const float len = sqrtf(fmaf(g.z, g.z, fmaf(g.y, g.y, g.x * g.x)));
+        if (hit && len > 0.0f) {
+            const float inv = 1.0f / len;
+            nrm = {g.x * inv, g.y * inv, g.z * inv};
+        }
+    }
+    if (live) {
+        out_n[at] = nrm.x;
+        out_n[nstride + at] = nrm.y;
+        out_n[2 * nstride + at] = nrm.z;
+    }
+}
+
+#endif  // SDFK_RAYDEV_H

@@ -1,0 +1,452 @@
+"""Sphere tracing of geometries on the GPU: ray casts and depth / normal images (kernels: csrc/sdfk_rays.inc).
+
+    from aegolius_amd import render
+    cam = render.Camera(eye=(2.2, 1.6, 1.9), target=(0, 0, 0), fov=40)
+    img = render.render(geometry, cam, 1920, 1080, t_min=0.0, t_max=8.0)
+    img.save_pgm("part.pgm", img.shade(light=(1, 1, 2)))
+    hits = render.cast(geometry, origins, directions, t_max=8.0)          # arbitrary rays, (3, N) arrays
+
+No field and no grid are made: the geometry's program (create()'s own) is evaluated along every ray.
+
+The marching rule (one definition: the kernels, tests/render_reference.py and this text), per ray, in float32:
+
+    t = t_min
+    repeat at most max_steps times:
+        f   = field(o + t d)                      # fmaf(t, d, o) per component
+        thr = max(eps, cone * t)
+        if f <= thr: status = HIT; stop           # a ray that starts inside or within thr of the surface hits at t_min
+        t   = t + f / L                           # fmaf(f, float32(1 / L), t); steps += 1
+        if t > t_max: status = MISS; stop
+    otherwise: status = LIMIT                     # never folded into hit or miss
+
+L is a Lipschitz bound of the field with respect to the point, so that a step can never cross the surface. The lowering
+tracks it (`LoweredProgram.lipschitz`: 1 for distance functions under rigid transforms, the matrix 2-norm under shear,
+sqrt(2) for an extrusion, the sum for SUM, ...). Where it is infinite — twist, bend, repetition cells, sign, nearest
+instance — the caller must pass `lipschitz=` (the usual "step scale" of sphere tracers; too small a value lets rays
+pass through the surface, and that is the caller's responsibility). Trees that need a staged evaluation (signed,
+conv_*, custom_*, Python callables) are refused with autodiff.UnsupportedOpError, as the derivative paths do.
+
+`steps` counts the advances of t (int32): 0 for a ray that hits at t_min, so a hit ray cost steps + 1 evaluations.
+2-D geometries ignore z: they trace as infinite prisms along z.
+
+Pixel (ix, iy) of a W x H image, row iy = 0 at the top; a = (2 ix + 1) / W - 1, b = 1 - (2 iy + 1) / H; with the unit
+vectors fwd = (target - eye) / |target - eye|, right = fwd x up / |fwd x up|, upv = right x fwd:
+
+    perspective : o = eye,                  d = normalised(fwd + a du + b dv),  du = right tan(fov / 2) W / H,
+                                                                                dv = upv tan(fov / 2)
+    orthographic: o = eye + a du + b dv,    d = fwd,                            du = right (height / 2) W / H,
+                                                                                dv = upv height / 2
+
+(`fov`: the vertical field of view in degrees; `height`: the world height of the orthographic image.) `render` hands
+the kernel the record {eye, fwd, du, dv} in float32 and the kernel generates the rays itself — no ray array exists;
+`Camera.rays` is the same formula on the host in float64. The hit threshold is the pixel's footprint: `cone` defaults
+to tan(fov / 2) / H, half the angular size of a pixel (orthographic: `eps` defaults to height / (2 H), half a pixel).
+"""
+import ctypes
+
+import numpy as np
+
+from . import _engine, _lipschitz, _ops
+from ._eval import config, program_for
+from ._lower import OWNED, NeedsStage, _deep
+from .autodiff import UnsupportedOpError, _Coords, _TracingLowerer      # (autodiff.py marks both as used from here)
+
+MISS, HIT, LIMIT = 0, 1, 2
+STENCIL_FLOOR = np.float32(2.0 ** -16)        # csrc/sdfk_raydev.h sdfk_ray_stencil_width
+
+
+# ---- lowering ---------------------------------------------------------------------------------------------------------
+class _RayLowerer(_TracingLowerer):
+    """Remembers the first instruction whose destination has no finite Lipschitz bound."""
+
+    def __init__(self):
+        _TracingLowerer.__init__(self, True)
+        self.first_unbounded = None
+
+    def emit(self, opname, a, b=0, c=0, params=(), _fold=True):
+        _TracingLowerer.emit(self, opname, a, b, c, params, _fold)
+        if self.first_unbounded is None and self.code:
+            word = self.code[-1][0]
+            info = _ops.OPS[word & 255]
+            dst = (word >> 8) & 255
+            bound = (self.lip_c if info.kind == "C_C" else self.lip_v).get(dst, _lipschitz.INF)
+            if not np.isfinite(bound):
+                self.first_unbounded = (len(self.code) - 1, info.name, self.origin[-1] if self.origin else "the geometry")
+
+
+def lower(geometry):
+    """-> (LoweredProgram — create()'s own program —, first unbounded instruction (index, opcode, origin) or None)."""
+    L = _RayLowerer()
+    try:
+        v = _deep(lambda: L.lower_node(geometry, 0, OWNED))
+    except NeedsStage as exc:
+        raise UnsupportedOpError("%r needs a staged evaluation (signed / conv_* / custom_* / Python callables cannot be "
+                                 "traced along rays)" % (exc.expr.name,)) from None
+    return L.finish(v), L.first_unbounded
+
+
+def _bound(low, first, lipschitz):
+    if lipschitz is not None:
+        L = float(lipschitz)
+        if not (np.isfinite(L) and L > 0.0):
+            raise ValueError("lipschitz must be finite and positive; got %r" % (lipschitz,))
+        return L
+    if not np.isfinite(low.lipschitz):
+        if first is not None:
+            where = "instruction %d (%s, from %s) has no finite Lipschitz bound" % first
+        else:
+            where = "its field has no finite Lipschitz bound"
+        raise ValueError("this geometry cannot be sphere-traced with a derived step: %s; pass lipschitz= (an upper bound of "
+                         "|grad f| over the region the rays cross)" % where)
+    if not low.lipschitz > 0.0:
+        raise ValueError("the field's Lipschitz bound is 0 (a constant field has no surface); pass lipschitz=")
+    return float(low.lipschitz)
+
+
+def _options(t_min, t_max, eps, cone, max_steps):
+    t_min, t_max, eps, cone = float(t_min), float(t_max), float(eps), float(cone)
+    if not (np.isfinite(t_min) and np.isfinite(t_max)):
+        raise ValueError("t_min and t_max must be finite")
+    if t_max < t_min:
+        raise ValueError("t_max (%g) < t_min (%g)" % (t_max, t_min))
+    if int(max_steps) < 1:
+        raise ValueError("max_steps must be at least 1; got %r" % (max_steps,))
+    if not (np.isfinite(eps) and eps >= 0.0 and np.isfinite(cone) and cone >= 0.0):
+        raise ValueError("eps and cone must be finite and not negative")
+    return tuple(float(np.float32(x)) for x in (t_min, t_max, eps, cone)) + (int(max_steps),)   # as the kernel sees them
+
+
+def _program(low):
+    prog = program_for(low)
+    bad = ctypes.c_int(-1)
+    rc = _engine.lib().sdfk_program_rays_check(prog.handle, ctypes.byref(bad))
+    if rc == 1:
+        raise UnsupportedOpError("the program reads an auxiliary field (staged evaluation): it exists on a grid only")
+    _engine.check(rc, "sdfk_program_rays_check")
+    return prog
+
+
+def stencil_width(t, points, eps, cone):
+    """Half-width h of the kernels' normal stencil at the hits (t (N,), points (3, N)), in their float32 arithmetic:
+    max(thr, 2^-16 max(|x|, |y|, |z|)) with thr = max(eps, cone t)."""
+    t = np.asarray(t, dtype=np.float32)
+    p = np.abs(np.asarray(points, dtype=np.float32))
+    thr = np.maximum(np.float32(eps), np.float32(cone) * t)
+    return np.maximum(thr, STENCIL_FLOOR * p.max(axis=0))
+
+
+# ---- results ----------------------------------------------------------------------------------------------------------
+class RayHits:
+    """Result of cast(): t (N,) float32 — where the ray stopped —, status (N,) uint8 (MISS 0: t passed t_max, HIT 1,
+    LIMIT 2: max_steps reached), steps (N,) int32 (advances made), normals (3, N) float32 or None (zero for non-hits).
+    With resident=True, t is a DeviceField and normals a DeviceVectorField; status and steps are host arrays."""
+
+    def __init__(self, t, status, steps, normals, origins, directions):
+        self.t, self.status, self.steps, self.normals = t, status, steps, normals
+        self.origins, self.directions = origins, directions
+
+    def __repr__(self):
+        return "RayHits(%d rays, %d hits, %d at the step limit)" % (self.status.size, int(np.count_nonzero(self.status == HIT)),
+                                                                    int(np.count_nonzero(self.status == LIMIT)))
+
+    def points(self):
+        """o + t d of the rays that hit, (3, M) float32 (computed in float64 from the float32 o, d, t), in ray order."""
+        def host(x):
+            return x.numpy() if isinstance(x, (_engine.DeviceField, _engine.DeviceVectorField)) else np.asarray(x)
+        hit = self.status == HIT
+        o = host(self.origins).astype(np.float32).astype(np.float64)[:, hit]
+        d = host(self.directions).astype(np.float32).astype(np.float64)[:, hit]
+        return (o + host(self.t).astype(np.float64)[hit] * d).astype(np.float32)
+
+
+class Camera:
+    """A pinhole camera (or, from Camera.orthographic, a parallel one); see the module text for the pixel formula."""
+
+    def __init__(self, eye, target, up=(0, 0, 1), fov=40.0):
+        self.eye = np.asarray(eye, dtype=np.float64).reshape(3)
+        self.target = np.asarray(target, dtype=np.float64).reshape(3)
+        self.up = np.asarray(up, dtype=np.float64).reshape(3)
+        self.fov, self.height, self.ortho = float(fov), None, False
+        if not 0.0 < self.fov < 180.0:
+            raise ValueError("fov is the vertical field of view in degrees, between 0 and 180; got %r" % (fov,))
+        self._basis()
+
+    @classmethod
+    def orthographic(cls, eye, target, up=(0, 0, 1), height=2.0):
+        self = cls(eye, target, up, 40.0)
+        self.fov, self.height, self.ortho = None, float(height), True
+        if not (np.isfinite(self.height) and self.height > 0.0):
+            raise ValueError("height is the world height of the image, positive; got %r" % (height,))
+        return self
+
+    def _basis(self):
+        fwd = self.target - self.eye
+        n = np.linalg.norm(fwd)
+        if not (np.isfinite(n) and n > 0.0):
+            raise ValueError("eye and target must be two different finite points")
+        self.fwd = fwd / n
+        right = np.cross(self.fwd, self.up)
+        n = np.linalg.norm(right)
+        if not (np.isfinite(n) and n > 1e-12 * max(1.0, np.linalg.norm(self.up))):
+            raise ValueError("up is parallel to the viewing direction")
+        self.right = right / n
+        self.upv = np.cross(self.right, self.fwd)
+
+    def _check(self, width, height):
+        width, height = int(width), int(height)
+        if not (1 <= width <= 32768 and 1 <= height <= 32768):
+            raise ValueError("image sizes from 1 to 32768; got %d x %d" % (width, height))
+        return width, height
+
+    def frame(self, width, height):
+        """(du, dv) in float64: the right / up vectors scaled by half the extent of the image plane."""
+        width, height = self._check(width, height)
+        half = 0.5 * self.height if self.ortho else np.tan(np.radians(0.5 * self.fov))
+        return self.right * (half * width / height), self.upv * half
+
+    def record(self, width, height):
+        """The 12 float32 {eye, fwd, du, dv} the kernel generates its rays from."""
+        du, dv = self.frame(width, height)
+        return np.concatenate([self.eye, self.fwd, du, dv]).astype(np.float32)
+
+    def footprint(self, width, height):
+        """(eps, cone) of a pixel: half its world size (orthographic) or half its angular size (perspective)."""
+        width, height = self._check(width, height)
+        if self.ortho:
+            return 0.5 * self.height / height, 0.0
+        return 0.0, float(np.tan(np.radians(0.5 * self.fov)) / height)
+
+    def rays(self, width, height):
+        """(origins, directions), both (3, W H) float64, row-major pixel order (index iy W + ix, row 0 at the top)."""
+        width, height = self._check(width, height)
+        du, dv = self.frame(width, height)
+        a = (2.0 * np.arange(width) + 1.0) / width - 1.0
+        b = 1.0 - (2.0 * np.arange(height) + 1.0) / height
+        a, b = np.meshgrid(a, b, indexing="xy")                 # (H, W)
+        q = a.ravel()[None] * du[:, None] + b.ravel()[None] * dv[:, None]
+        if self.ortho:
+            return self.eye[:, None] + q, np.repeat(self.fwd[:, None], width * height, axis=1)
+        w = self.fwd[:, None] + q
+        return np.repeat(self.eye[:, None], width * height, axis=1), w / np.linalg.norm(w, axis=0)
+
+
+class Image:
+    """Result of render(): depth (H, W) float32 — t of the hit, +inf where the ray did not hit (miss or step limit) —,
+    status (H, W) uint8, steps (H, W) int32, normals (H, W, 3) float32 or None (zero where not hit), t (H, W) float32
+    (where every ray stopped, hit or not) and the camera, eps and cone it was made with."""
+
+    def __init__(self, depth, status, steps, normals, t=None, camera=None, eps=0.0, cone=0.0):
+        self.depth, self.status, self.steps, self.normals = depth, status, steps, normals
+        self.t = depth if t is None else t
+        self.camera, self.eps, self.cone = camera, eps, cone
+
+    def __repr__(self):
+        h, w = self.status.shape
+        return "Image(%d x %d, %d hits)" % (w, h, int(np.count_nonzero(self.status == HIT)))
+
+    def points(self):
+        """Hit points (3, M) float32 in row-major pixel order, from Camera.rays in float64."""
+        h, w = self.status.shape
+        o, d = self.camera.rays(w, h)
+        hit = (self.status == HIT).ravel()
+        return (o[:, hit] + self.t.ravel().astype(np.float64)[hit] * d[:, hit]).astype(np.float32)
+
+    def exact_normals(self, geometry):
+        """Replace the stencil normals by the unit gradient of `geometry` at the hit points
+        (autodiff.value_and_grad_points, normalised on the host as Mesh.compute_normals does). Raises that function's
+        UnsupportedOpError for trees without a dual rule."""
+        from .autodiff import value_and_grad_points
+        pts = np.ascontiguousarray(self.points(), dtype=np.float32)
+        _, grad = value_and_grad_points(geometry, pts)
+        g = np.asarray(grad, dtype=np.float64).reshape(3, -1).T
+        norm = np.linalg.norm(g, axis=1, keepdims=True)
+        unit = np.divide(g, norm, out=np.zeros_like(g), where=norm > 0).astype(np.float32)
+        out = np.zeros(self.status.shape + (3,), dtype=np.float32)
+        out[self.status == HIT] = unit
+        self.normals = out
+        return out
+
+    def shade(self, light=(1.0, 1.0, 2.0), ambient=0.15, color=None, background=0.0, dtype=np.uint8):
+        """Lambert shading from normals and status on the host: ambient + (1 - ambient) max(0, n . l) at the hits (l the
+        unit vector TOWARD the light), `background` elsewhere. -> (H, W), or (H, W, 3) with an RGB `color` in [0, 1];
+        uint8 (0..255, rounded) or float32 in [0, 1]."""
+        if self.normals is None:
+            raise ValueError("shade needs normals: render(..., normals=True) or exact_normals()")
+        l = np.asarray(light, dtype=np.float64).reshape(3)
+        n = np.linalg.norm(l)
+        if not n > 0.0:
+            raise ValueError("the light direction is the zero vector")
+        lam = np.clip(np.asarray(self.normals, dtype=np.float64).dot(l / n), 0.0, 1.0)
+        value = np.where(self.status == HIT, float(ambient) + (1.0 - float(ambient)) * lam, float(background))
+        if color is not None:
+            rgb = np.asarray(color, dtype=np.float64).reshape(3)
+            value = np.where((self.status == HIT)[..., None], value[..., None] * rgb, float(background))
+        value = np.clip(value, 0.0, 1.0)
+        if np.dtype(dtype) == np.uint8:
+            return np.rint(value * 255.0).astype(np.uint8)
+        return value.astype(np.float32)
+
+    @staticmethod
+    def _pnm(path, pixels, magic, channels):
+        px = np.asarray(pixels)
+        if px.dtype != np.uint8:
+            px = np.rint(np.clip(px.astype(np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+        want = 2 if channels == 1 else 3
+        if px.ndim != want or (channels == 3 and px.shape[2] != 3):
+            raise ValueError("expected %s pixels; got shape %r" % ("(H, W)" if channels == 1 else "(H, W, 3)", px.shape))
+        with open(path, "wb") as f:
+            f.write(("%s\n%d %d\n255\n" % (magic, px.shape[1], px.shape[0])).encode("ascii"))
+            f.write(np.ascontiguousarray(px).tobytes())
+
+    def save_pgm(self, path, pixels=None):
+        """Binary PGM (P5) of (H, W) pixels, uint8 or float in [0, 1]; default: shade()."""
+        self._pnm(path, self.shade() if pixels is None else pixels, "P5", 1)
+
+    def save_ppm(self, path, pixels=None):
+        """Binary PPM (P6) of (H, W, 3) pixels; default: shade(color=(1, 1, 1))."""
+        self._pnm(path, self.shade(color=(1.0, 1.0, 1.0)) if pixels is None else pixels, "P6", 3)
+
+    def save_npz(self, path):
+        arrays = {"depth": self.depth, "status": self.status, "steps": self.steps, "t": self.t}
+        if self.normals is not None:
+            arrays["normals"] = self.normals
+        np.savez_compressed(path, **arrays)
+
+
+# ---- device plumbing ----------------------------------------------------------------------------------------------------
+class _Outputs:
+    def __init__(self, n, normals):
+        L = _engine.lib()
+        self.n = n
+        self.t = self.normals = self.d_status = self.d_steps = None
+        try:
+            self.t = _engine.DeviceField(n, config.device)
+            self.normals = _engine.DeviceVectorField(n, config.device) if normals else None
+            self.d_status = L.sdfk_malloc(max(n, 64))
+            self.d_steps = L.sdfk_malloc(max(n, 16) * 4)
+            if not self.d_status or not self.d_steps:
+                raise _engine.SdfkError("render: out of device memory")
+        except BaseException:
+            self.free()
+            raise
+
+    def small(self):
+        status = np.empty(self.n, dtype=np.uint8)
+        steps = np.empty(self.n, dtype=np.int32)
+        if self.n:
+            L = _engine.lib()
+            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(status), _engine._vp(self.d_status), self.n), "sdfk_memcpy_d2h")
+            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(steps), _engine._vp(self.d_steps), self.n * 4), "sdfk_memcpy_d2h")
+        return status, steps
+
+    def free(self, keep=False):
+        L = _engine.lib()
+        for name in ("d_status", "d_steps"):
+            p = getattr(self, name, None)
+            if p:
+                L.sdfk_free(_engine._vp(p))
+                setattr(self, name, None)
+        if not keep:
+            for field in (self.t, self.normals):
+                if field is not None:
+                    field.free()
+
+
+def _normal_args(out):
+    if out.normals is None:
+        return None, 0
+    return _engine._vp(out.normals.ptr), out.normals.stride
+
+
+# ---- public interface ---------------------------------------------------------------------------------------------------
+def cast(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0.0, max_steps=256, lipschitz=None,
+         normals=False, resident=False):
+    """First hit of arbitrary rays with `geometry`. `origins`, `directions`: (3, N) host arrays (used as float32) or
+    DeviceVectorFields; the directions must be unit vectors (checked for host arrays: | |d|^2 - 1 | <= 1e-5).
+    -> RayHits. See the module text for the marching rule, `lipschitz` and the refusals."""
+    t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
+    low, first = lower(geometry)
+    bound = _bound(low, first, lipschitz)
+    for name, x in (("origins", origins), ("directions", directions)):
+        if not isinstance(x, _engine.DeviceVectorField):
+            shape = np.shape(x)
+            if len(shape) != 2 or shape[0] != 3:
+                raise ValueError("%s must have shape (3, N); got %r" % (name, shape))
+    if not isinstance(directions, _engine.DeviceVectorField):
+        d32 = np.asarray(directions, dtype=np.float32).astype(np.float64)
+        off = np.abs((d32 * d32).sum(axis=0) - 1.0)
+        if off.size and not np.all(off <= 1e-5):
+            raise ValueError("directions must be unit vectors: ray %d has |d|^2 = %.9g" %
+                             (int(np.argmax(~(off <= 1e-5))), float((d32 * d32).sum(axis=0)[np.argmax(~(off <= 1e-5))])))
+    n_o = origins.n if isinstance(origins, _engine.DeviceVectorField) else int(np.shape(origins)[1])
+    n_d = directions.n if isinstance(directions, _engine.DeviceVectorField) else int(np.shape(directions)[1])
+    if n_o != n_d:
+        raise ValueError("%d origins for %d directions" % (n_o, n_d))
+    prog = _program(low)
+    _engine.require_gpu()
+    L = _engine.lib()
+    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
+    vp = _engine._vp
+    co, cd, out = None, None, None
+    try:
+        co = _Coords(origins)
+        cd = _Coords(directions)
+        out = _Outputs(n_o, normals)
+        d_n, nstride = _normal_args(out)
+        _engine.check(L.sdfk_trace_rays_device(prog.handle, vp(co.ptr), co.stride, vp(cd.ptr), cd.stride, n_o, t_min, t_max,
+                                               eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(out.t.ptr),
+                                               vp(out.d_status), vp(out.d_steps), d_n, nstride, None, config.mode),
+                      "sdfk_trace_rays_device")
+        _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        status, steps = out.small()
+        if resident:
+            out.free(keep=True)
+            return RayHits(out.t, status, steps, out.normals, origins, directions)
+        t = out.t.numpy()
+        nrm = out.normals.numpy() if normals else None
+        out.free()
+        return RayHits(t, status, steps, nrm, origins, directions)
+    except BaseException:
+        if out is not None:
+            out.free()
+        raise
+    finally:
+        for c in (co, cd):
+            if c is not None:
+                c.free()
+
+
+def render(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=256, lipschitz=None, normals=True, eps=None,
+           cone=None):
+    """Depth / normal image of `geometry` from `camera`: the kernel generates the W x H rays from the camera record.
+    `eps` / `cone` default to the pixel's footprint (Camera.footprint). -> Image."""
+    width, height = camera._check(width, height)
+    fe, fc = camera.footprint(width, height)
+    eps = fe if eps is None else eps
+    cone = fc if cone is None else cone
+    t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
+    low, first = lower(geometry)
+    bound = _bound(low, first, lipschitz)
+    prog = _program(low)
+    _engine.require_gpu()
+    L = _engine.lib()
+    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
+    vp = _engine._vp
+    n = width * height
+    rec = camera.record(width, height)
+    out = _Outputs(n, normals)
+    try:
+        d_n, nstride = _normal_args(out)
+        _engine.check(L.sdfk_trace_camera_device(prog.handle, _engine._ptr(rec), width, height, 1 if camera.ortho else 0, t_min,
+                                                 t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(out.t.ptr),
+                                                 vp(out.d_status), vp(out.d_steps), d_n, nstride, None, config.mode),
+                      "sdfk_trace_camera_device")
+        _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        status, steps = out.small()
+        t = out.t.numpy().reshape(height, width)
+        nrm = np.ascontiguousarray(out.normals.numpy().T).reshape(height, width, 3) if normals else None
+    finally:
+        out.free()
+    status = status.reshape(height, width)
+    depth = np.where(status == HIT, t, np.float32(np.inf)).astype(np.float32)
+    return Image(depth, status, steps.reshape(height, width), nrm, t=t, camera=camera, eps=float(eps), cone=float(cone))

@@ -99,6 +99,9 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
 #define SDFK_FLAVOUR_ROWS_MASK 7   /* test aid (sdfk_debug_row_masks) */
 #define SDFK_FLAVOUR_ROWS2D_ARRAY 8 /* the row-block kernel built for flat grids (sdfk_eval_device_rows2d) */
 #define SDFK_FLAVOUR_ROWS2D_GRID 9
+#define SDFK_FLAVOUR_RAYS 10       /* sdfk_spec_rays / sdfk_spec_raycam: sphere tracing (sdfk_trace_rays_device /
+                                      sdfk_trace_camera_device) around the straight-line body, one ray per lane; needs no
+                                      cull sites and has no FLAGS / XY build. Not part of sdfk_program_compile_check. */
 /* OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (one bit per point, value <= threshold, instead of
    the field — what sdfk_eval_device_select / sdfk_eval_grid_select launch). A translation unit of its own: the field
    kernels carry none of it (as a run-time branch it cost the 20-primitive tree 10 % at 1025^3). */
@@ -486,6 +489,44 @@ int sdfk_eval_grid_contour2d_finish(sdfk_program* prog, const float* ax0, int64_
                                     int64_t n_vertices, int64_t n_segments, float* d_vertices, int64_t vertex_capacity,
                                     void* d_segments, int64_t segment_capacity, int segment_bytes, void* d_scratch,
                                     void* stream, int mode);
+
+/* ---- sphere tracing ----------------------------------------------------------------------------
+ * First hit of rays with the surface of the program's field, which must be a distance bound: |f(p) - f(q)| <=
+ * L |p - q| with a finite L the caller knows (aegolius_amd._lower tracks it per program). Per ray, in fp32:
+ *     t = t_min
+ *     repeat at most max_steps times:
+ *         f = field(o + t d);  thr = max(eps, cone * t)
+ *         if f <= thr: status 1 (hit), stop
+ *         t = t + f * inv_lipschitz;  steps += 1
+ *         if t > t_max: status 0 (miss), stop
+ *     otherwise: status 2 (step limit)
+ * Outputs, one entry per ray: d_t (fp32, the parameter the ray stopped at), d_status (1 byte), d_steps (int32, the
+ * advances made: 0 for a ray that starts within thr of the solid) and, unless d_normals is NULL, the unit normal at
+ * the hit as three rows of normal_stride floats: the four-point tetrahedron difference of the field with the
+ * half-width h = max(thr, 2^-16 * max(|x|, |y|, |z|)) of the hit point, the zero vector for rays that did not hit.
+ * Directions must be unit vectors (not checked on the device). Asynchronous on `stream`. `mode` selects the kernel as
+ * for sdfk_eval_device (SDFK_MODE_NOCULL = SDFK_MODE_SPECIALIZED here: rays are never culled): the interpreter
+ * kernel and the specialised one (SDFK_FLAVOUR_RAYS) give the same bits; programs beyond the interpreter's register
+ * file run on the specialised kernel only. Arguments are validated on the host — t_max < t_min, max_steps <= 0, a
+ * non-finite or non-positive inv_lipschitz, negative eps / cone return -1 and launch nothing. */
+/* 0: the program can be traced; 1: it reads an auxiliary field (V_FIELD: staged evaluation, defined on a grid only),
+ * *first_bad_op (nullable) = that instruction. */
+int sdfk_program_rays_check(sdfk_program* prog, int* first_bad_op);
+/* n rays from two (3, n) device arrays (row r of the origins at d_origins + r * origin_stride, likewise directions). */
+int sdfk_trace_rays_device(sdfk_program* prog, const float* d_origins, int64_t origin_stride, const float* d_directions,
+                           int64_t direction_stride, int64_t n, float t_min, float t_max, float eps, float cone,
+                           float inv_lipschitz, int max_steps, float* d_t, unsigned char* d_status, int* d_steps,
+                           float* d_normals, int64_t normal_stride, void* stream, int mode);
+/* width x height rays generated in the kernel from `camera`, 12 host floats {eye, fwd, du, dv}: for pixel (ix, iy), row
+ * 0 at the top, a = (2 ix + 1) / width - 1 and b = 1 - (2 iy + 1) / height;
+ *     perspective : o = eye,                d = normalised(fwd + a du + b dv)
+ *     orthographic: o = eye + a du + b dv,  d = fwd
+ * (fwd a unit vector). Outputs in row-major pixel order (index iy * width + ix); every wave traces one tile of 8 x 8
+ * pixels. */
+int sdfk_trace_camera_device(sdfk_program* prog, const float* camera, int width, int height, int orthographic, float t_min,
+                             float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_t,
+                             unsigned char* d_status, int* d_steps, float* d_normals, int64_t normal_stride, void* stream,
+                             int mode);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,133 @@
+"""Sphere-tracing benchmark (aegolius_amd.render): one scene per call, so that a job can give every scene a
+time limit of its own.
+    python tools/bench_render.py cfg2 [--width 1920 --height 1080 --reps 7 --warmup 2 --modes interpret,specialised]
+scenes: cfg2, cfg5, union200, union1000. Per kernel (interpreter / specialised): median ms per frame from device events
+around the launch alone (outputs pre-allocated, kernel already built), rays/s, point evaluations (sum of steps + 1 per ray
++ 4 per shaded hit) and evaluations/s; the yardstick — the plain field kernel of the same program (MODE_INTERPRET /
+MODE_NOCULL) on a (3, M) array of M = that many random points — and the ratio of the two rates; the wave efficiency of the
+8 x 8 tile mapping against a row-major one, from the steps image. Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EYE = (2.2, 1.6, 1.9)
+
+
+def scene(name):
+    import aegolius_amd.cores as ns
+    from aegolius_amd import workloads
+    return {"cfg2": lambda: workloads.cfg2_tree(ns), "cfg5": lambda: workloads.cfg5_tree(ns),
+            "union200": lambda: workloads.sphere_union(ns, count=200),
+            "union1000": lambda: workloads.sphere_union(ns, count=1000)}[name]()
+
+
+def wave_efficiency(steps):
+    """sum(steps) / sum over waves of 64 max(steps in the wave): 8 x 8 tiles, and 64 consecutive pixels of the row-major
+    order (the lanes a wave would get without the tile mapping). Pixels beyond the image count as idle lanes."""
+    h, w = steps.shape
+    total = float(steps.sum())
+    padded = np.zeros(((h + 7) // 8 * 8, (w + 7) // 8 * 8), dtype=np.int64)
+    padded[:h, :w] = steps
+    tiles = padded.reshape(padded.shape[0] // 8, 8, padded.shape[1] // 8, 8).max(axis=(1, 3))
+    flat = np.zeros((h * w + 63) // 64 * 64, dtype=np.int64)
+    flat[:h * w] = steps.ravel()
+    rows = flat.reshape(-1, 64).max(axis=1)
+    return total / (64.0 * tiles.sum()), total / (64.0 * rows.sum())
+
+
+def median_ms(launch, reps, warmup):
+    from aegolius_amd import _engine
+    for _ in range(warmup):
+        launch()
+    _engine.check(_engine.lib().sdfk_sync(None), "sdfk_sync")
+    out = []
+    for _ in range(reps):
+        a, b = _engine.Event(), _engine.Event()
+        a.record()
+        launch()
+        b.record()
+        _engine.check(_engine.lib().sdfk_sync(None), "sdfk_sync")
+        out.append(a.elapsed_ms(b))
+    return float(np.median(out)), float(min(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scene")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--t-max", type=float, default=8.0)
+    ap.add_argument("--max-steps", type=int, default=256)
+    ap.add_argument("--modes", default="interpret,specialised")
+    args = ap.parse_args()
+    import __graft_entry__
+    __graft_entry__.build()
+    from aegolius_amd import _engine, render
+    from aegolius_amd._eval import config, program_for
+    _engine.require_gpu()
+    L = _engine.lib()
+    vp = _engine._vp
+    geo = scene(args.scene)
+    low, _ = render.lower(geo)
+    prog = program_for(low)
+    cam = render.Camera(EYE, (0, 0, 0), (0, 0, 1), 40.0)
+    W, H = args.width, args.height
+    n = W * H
+    eps, cone = cam.footprint(W, H)
+    rec = cam.record(W, H)
+    inv = float(np.float32(1.0 / low.lipschitz))
+    out = render._Outputs(n, True)
+    result = {"scene": args.scene, "width": W, "height": H, "instructions": int(low.code.shape[0]), "lipschitz": low.lipschitz,
+              "chain_members": prog.chain_members, "device": "MI355X (gfx950), 1 GPU", "kernels": {}}
+    try:
+        for name in args.modes.split(","):
+            ray_mode = {"interpret": _engine.MODE_INTERPRET, "specialised": _engine.MODE_SPECIALIZED}[name]
+            field_mode = {"interpret": _engine.MODE_INTERPRET, "specialised": _engine.MODE_NOCULL}[name]
+            k = {}
+            if name == "specialised":
+                k["build_bytes"], k["build_seconds"] = prog.compile_flavour(_engine.FLAVOUR_RAYS)
+
+            def launch():
+                _engine.check(L.sdfk_trace_camera_device(prog.handle, _engine._ptr(rec), W, H, 0, 0.0, float(np.float32(args.t_max)),
+                                                         float(np.float32(eps)), float(np.float32(cone)), inv, args.max_steps,
+                                                         vp(out.t.ptr), vp(out.d_status), vp(out.d_steps), vp(out.normals.ptr),
+                                                         out.normals.stride, None, ray_mode), "sdfk_trace_camera_device")
+            k["ms"], k["ms_min"] = median_ms(launch, args.reps, args.warmup)
+            status, steps = out.small()
+            evals = int(steps.sum()) + n + 4 * int(np.count_nonzero(status == render.HIT))
+            k.update(rays_per_s=n / (k["ms"] * 1e-3), evaluations=evals, evaluations_per_s=evals / (k["ms"] * 1e-3),
+                     hits=int(np.count_nonzero(status == render.HIT)), step_limit=int(np.count_nonzero(status == render.LIMIT)),
+                     mean_steps=float(steps.mean()), max_steps=int(steps.max()))
+            k["wave_efficiency_tiles"], k["wave_efficiency_rows"] = wave_efficiency(steps.reshape(H, W))
+            # yardstick: the plain field kernel of the same program on as many points
+            rng = np.random.default_rng(1)
+            co = _engine.DeviceVectorField.from_host(rng.uniform(-1.0, 1.0, (3, evals)).astype(np.float32), config.device)
+            field = _engine.DeviceField(evals, config.device)
+            try:
+                def plain():
+                    prog.eval_device(co.row_ptr(0), evals, co.stride, field.ptr, mode=field_mode)
+                k["field_ms"], _ = median_ms(plain, args.reps, args.warmup)
+            finally:
+                co.free()
+                field.free()
+            k["field_points_per_s"] = evals / (k["field_ms"] * 1e-3)
+            k["ratio_to_field_kernel"] = k["evaluations_per_s"] / k["field_points_per_s"]
+            result["kernels"][name] = k
+    finally:
+        out.free()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    t0 = time.time()
+    main()
+    print("# %.1f s" % (time.time() - t0), file=sys.stderr)
