@@ -4,6 +4,7 @@ This is the only place the Python layer touches native code. There is no CPU fal
 shared library is missing or no MI355X is visible, evaluation raises.
 """
 import atexit
+import contextlib
 import ctypes
 import importlib.util
 import os
@@ -223,6 +224,152 @@ def _ptr(a):
     return a.ctypes.data_as(_vp) if a is not None and a.size else None
 
 
+def _release(owner, attr, destroy):
+    """Hand the handle `owner.<attr>` to the library's `destroy`, once (free() and every __del__ here). Never raises,
+    and does nothing once the library is gone (interpreter exit)."""
+    try:
+        h = getattr(owner, attr, None)
+        setattr(owner, attr, None)
+        if h and _lib is not None:
+            getattr(_lib, destroy)(_vp(h))
+    except Exception:
+        pass
+
+
+def coords_n(shape):
+    """N of a (3, N) coordinate array's shape."""
+    if len(shape) != 2 or shape[0] != 3:
+        raise ValueError("coordinates must have shape (3, N); got %r" % (tuple(shape),))
+    return int(shape[1])
+
+
+def host_coords(co, dtype=None):
+    """A (3, N) host coordinate array, checked and contiguous: float32 / float64 pass through and anything else becomes
+    float64 (what sdfk_eval_host takes), or everything becomes `dtype` (the staging paths upload float32)."""
+    co = np.asarray(co)
+    coords_n(co.shape)
+    if dtype is None and co.dtype not in (np.float32, np.float64):
+        dtype = np.float64
+    return np.ascontiguousarray(co, dtype=dtype)
+
+
+def axis_args(axes):
+    """Per-axis tables of a grid -> (contiguous float32 tables, their flat (ptr, size, ptr, size, ...) C arguments).
+    The pointers keep their tables alive (numpy's data_as holds a reference to its array)."""
+    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+    args = []
+    for a in ax:
+        args += [_ptr(a), a.size]
+    return ax, tuple(args)
+
+
+def row_stride(n):
+    """Floats between the rows of a staged (rows, n) fp32 array: every row starts on a 256-byte line."""
+    return (n + 63) // 64 * 64
+
+
+class DeviceBuffer:
+    """`nbytes` of raw device memory — the only owner of device memory in the Python layer. `free()`, leaving a `with`
+    block or garbage collection releases it; `ptr` is None from then on and every use raises."""
+
+    def __init__(self, nbytes, device=None, what=""):
+        self.ptr, self.nbytes, self.device = None, int(nbytes), device if device is None else int(device)
+        self.what = what or type(self).__name__
+        if device is not None:
+            check(lib().sdfk_set_device(self.device), "sdfk_set_device")
+        self.ptr = lib().sdfk_malloc(self.nbytes) or None
+        if self.ptr is None:
+            raise SdfkError("%s: out of device memory (%d bytes): %s" % (self.what, self.nbytes, last_error()))
+
+    def at(self, byte_offset=0, nbytes=0):
+        """c_void_p of [byte_offset, byte_offset + nbytes) of the buffer, which must lie inside it."""
+        if not self.ptr:
+            raise SdfkError("%s has been freed" % self.what)
+        if byte_offset < 0 or nbytes < 0 or byte_offset + nbytes > self.nbytes:
+            raise SdfkError("%s: bytes [%d, %d) are outside its %d bytes" % (self.what, byte_offset, byte_offset + nbytes,
+                                                                             self.nbytes))
+        return _vp(self.ptr + byte_offset)
+
+    def _live(self):
+        self.at()
+        if self.device is not None:
+            check(lib().sdfk_set_device(self.device), "sdfk_set_device")
+
+    def upload(self, host, byte_offset=0):
+        """The bytes of a host array (C order), to `byte_offset` of the buffer."""
+        host = np.ascontiguousarray(host)
+        dst = self.at(byte_offset, host.nbytes)
+        if host.nbytes:
+            check(lib().sdfk_memcpy_h2d(dst, _ptr(host), host.nbytes), "sdfk_memcpy_h2d")
+
+    def download(self, out, byte_offset=0):
+        """Fill the C-contiguous host array `out` from `byte_offset` of the buffer -> out."""
+        if not out.flags.c_contiguous:
+            raise ValueError("%s: download needs a C-contiguous array" % self.what)
+        src = self.at(byte_offset, out.nbytes)
+        if out.nbytes:
+            check(lib().sdfk_memcpy_d2h(_ptr(out), src, out.nbytes), "sdfk_memcpy_d2h")
+        return out
+
+    def copy_from(self, device_ptr, nbytes, byte_offset=0):
+        """`nbytes` from the device pointer (int) `device_ptr`, to `byte_offset` of the buffer."""
+        dst = self.at(byte_offset, nbytes)
+        if nbytes:
+            check(lib().sdfk_memcpy_d2d(dst, _vp(device_ptr), nbytes), "sdfk_memcpy_d2d")
+
+    def _filled(self, fill, *args):
+        """self after fill(*args), freed if that raises: for constructors that fill what they allocate."""
+        try:
+            fill(*args)
+        except BaseException:
+            self.free()
+            raise
+        return self
+
+    def free(self):
+        _release(self, "ptr", "sdfk_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        self.free()
+
+
+class DeviceRows(DeviceBuffer):
+    """`rows` fp32 rows of `n` values in device memory, `stride` = row_stride(n) floats apart: the layout of every
+    coordinate, auxiliary-field, stream and vector array the kernels take."""
+
+    def __init__(self, rows, n, device=None, what=""):
+        self.rows, self.n, self.stride = int(rows), int(n), row_stride(int(n))
+        DeviceBuffer.__init__(self, self.rows * self.stride * 4, device, what)
+
+    def offset(self, r):
+        """Byte offset of row r."""
+        return 4 * r * self.stride
+
+    def row(self, r):
+        return self.at(self.offset(r), 4 * self.n)
+
+    def row_ptr(self, r):
+        return self.row(r).value
+
+    def upload_rows(self, host):
+        """A (k <= rows, n) host array, as float32 to rows 0 .. k - 1."""
+        for r, line in enumerate(np.ascontiguousarray(host, dtype=np.float32)):
+            self.upload(line, self.offset(r))
+
+    def download_rows(self, count=None):
+        """Rows 0 .. count - 1 (default: all) -> (count, n) float32 host array."""
+        out = np.empty((self.rows if count is None else count, self.n), dtype=np.float32)
+        for r, line in enumerate(out):
+            self.download(line, self.offset(r))
+        return out
+
+
 class Program:
     """Owning wrapper of an `sdfk_program*` (a lowered expression tree)."""
 
@@ -280,12 +427,7 @@ class Program:
     def eval_host(self, co, device=0, mode=MODE_AUTO):
         """co: (3, N) float32/float64 host array -> (N,) float32 field."""
         require_gpu()
-        co = np.asarray(co)
-        if co.ndim != 2 or co.shape[0] != 3:
-            raise ValueError("coordinates must have shape (3, N); got %r" % (co.shape,))
-        if co.dtype not in (np.float32, np.float64):
-            co = co.astype(np.float64)
-        co = np.ascontiguousarray(co)
+        co = host_coords(co)
         n = co.shape[1]
         out = np.empty(n, dtype=np.float32)
         check(lib().sdfk_eval_host(self._h, _ptr(co), 0 if co.dtype == np.float32 else 1, n, n, _ptr(out), device,
@@ -322,9 +464,8 @@ class Program:
                                                _vp(stream or 0), mode), "sdfk_eval_device_rows2d_xy")
 
     def eval_grid(self, axes, start, count, d_out, stream=None, mode=MODE_AUTO):
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
-        check(lib().sdfk_eval_grid(self._h, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                                   ax[2].size, start, count, _vp(d_out), _vp(stream or 0), mode), "sdfk_eval_grid")
+        _, tab = axis_args(axes)
+        check(lib().sdfk_eval_grid(self._h, *tab, start, count, _vp(d_out), _vp(stream or 0), mode), "sdfk_eval_grid")
 
     def _select(self, n, first, device, row_len=0, mode=MODE_AUTO):
         """Two-step protocol of the fused selection: `first(d_scratch, byref(count))` evaluates into flags and counts;
@@ -332,37 +473,21 @@ class Program:
         require_gpu()
         L = lib()
         check(L.sdfk_set_device(int(device)), "sdfk_set_device")
-        m = _i64(0)
-        d_scratch = L.sdfk_malloc(L.sdfk_eval_select_scratch(n, int(row_len)))
-        d_index = None
-        try:
-            if not d_scratch:
-                raise SdfkError("select: out of device memory")
-            first(_vp(d_scratch), ctypes.byref(m))
-            out = np.empty(m.value, dtype=np.int64)
-            if m.value:
-                d_index = L.sdfk_malloc(m.value * 8)
-                if not d_index:
-                    raise SdfkError("select: out of device memory")
-                check(L.sdfk_eval_select_finish(self._h, n, int(row_len), mode, m.value, _vp(d_index), m.value, _vp(d_scratch),
-                                                None), "sdfk_eval_select_finish")
-                check(L.sdfk_memcpy_d2h(_ptr(out), _vp(d_index), out.size * 8), "sdfk_memcpy_d2h")
-            return out
-        finally:
-            for d in (d_scratch, d_index):
-                if d:
-                    L.sdfk_free(_vp(d))
+
+        def finish(m, d_index, d_scratch):
+            check(L.sdfk_eval_select_finish(self._h, n, int(row_len), mode, m, d_index, m, d_scratch, None),
+                  "sdfk_eval_select_finish")
+        return _select(L.sdfk_eval_select_scratch(n, int(row_len)), first, finish)
 
     def select_grid(self, axes, threshold=0.0, start=0, count=None, device=0, mode=MODE_AUTO):
         """numpy.flatnonzero(field <= threshold) of the grid spanned by three per-axis tables, WITHOUT a field: the
         evaluation kernels write one flag bit per point, the compaction reads the flags (sdfk_eval_grid_select)."""
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+        ax, tab = axis_args(axes)
         total = ax[0].size * ax[1].size * ax[2].size
         count = total - start if count is None else count
 
         def first(d_scratch, m):
-            check(lib().sdfk_eval_grid_select(self._h, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                                              ax[2].size, start, count, float(threshold), None, 0, m, d_scratch, None,
+            check(lib().sdfk_eval_grid_select(self._h, *tab, start, count, float(threshold), None, 0, m, d_scratch, None,
                                               mode), "sdfk_eval_grid_select")
         grow = ax[2].size if ax[2].size > 1 else ax[1].size
         return self._select(count, first, device, row_len=grow if start % grow == 0 and count % grow == 0 else 0, mode=mode)
@@ -375,86 +500,23 @@ class Program:
         both). -> (vertices (V, D) float32, faces (F, D) int32, or int64 from 2^31 vertices on). `timings`: a dict that
         receives device-event milliseconds of count (evaluation to bits, count, scan) / emit / copy."""
         require_gpu()
-        L = lib()
-        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
-        dims = len(ax)
-        if dims not in (2, 3):
+        check(lib().sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(axes)
+        if len(ax) not in (2, 3):
             raise ValueError("mesh_grid: two or three axis tables")
-        shape = [a.size for a in ax]
-        tab = []
-        for a in ax:
-            tab += [_ptr(a), a.size]
-        lv = _c.c_float(level)
-        nv, nf = _i64(0), _i64(0)
-        bufs, ev = [], []
-
-        def alloc(nbytes):
-            p = L.sdfk_malloc(max(int(nbytes), 1))
-            if not p:
-                raise SdfkError("mesh: out of device memory (%d bytes)" % nbytes)
-            bufs.append(p)
-            return _vp(p)
-
-        def mark():
-            if timings is not None:
-                e = Event()
-                e.record()
-                ev.append(e)
-
-        try:
-            mark()
-            if dims == 3:
-                d_scratch = alloc(L.sdfk_eval_grid_isosurface_scratch(*shape))
-                check(L.sdfk_eval_grid_isosurface(self._h, *tab, lv, ctypes.byref(nv), ctypes.byref(nf), d_scratch, None, mode),
-                      "sdfk_eval_grid_isosurface")
-            else:
-                d_scratch = alloc(L.sdfk_eval_grid_contour2d_scratch(*shape))
-                check(L.sdfk_eval_grid_contour2d(self._h, *tab, lv, ctypes.byref(nv), ctypes.byref(nf), d_scratch, None, mode),
-                      "sdfk_eval_grid_contour2d")
-            mark()
-            V, F = nv.value, nf.value
-            wide = V > 0x7fffffff
-            d_v = alloc(V * dims * 4)
-            d_f = alloc(F * dims * (8 if wide else 4))
-            fin = L.sdfk_eval_grid_isosurface_finish if dims == 3 else L.sdfk_eval_grid_contour2d_finish
-            check(fin(self._h, *tab, lv, V, F, d_v, V, d_f, F, 8 if wide else 4, d_scratch, None, mode),
-                  "sdfk_eval_grid_isosurface_finish" if dims == 3 else "sdfk_eval_grid_contour2d_finish")
-            mark()
-            verts = np.empty((V, dims), dtype=np.float32)
-            faces = np.empty((F, dims), dtype=np.int64 if wide else np.int32)
-            if V:
-                check(L.sdfk_memcpy_d2h(_ptr(verts), d_v, verts.nbytes), "sdfk_memcpy_d2h")
-            if F:
-                check(L.sdfk_memcpy_d2h(_ptr(faces), d_f, faces.nbytes), "sdfk_memcpy_d2h")
-            mark()
-            if timings is not None:
-                for name, a, b in zip(("count", "emit", "copy"), ev, ev[1:]):
-                    timings[name] = a.elapsed_ms(b)
-            return verts, faces
-        finally:
-            for p in bufs:
-                L.sdfk_free(_vp(p))
+        lead = (self._h,) + tab
+        return extract_mesh("sdfk_eval_grid", [a.size for a in ax], level, lead, lead, (mode,), timings)
 
     def select_host(self, co, threshold=0.0, device=0, mode=MODE_AUTO):
         """The same for a (3, N) host array (uploaded once as float32; the row-length hint is detected like create())."""
         require_gpu()
-        co = np.asarray(co)
-        if co.ndim != 2 or co.shape[0] != 3:
-            raise ValueError("coordinates must have shape (3, N); got %r" % (co.shape,))
-        co32 = np.ascontiguousarray(co, dtype=np.float32)
+        co32 = host_coords(co, np.float32)
         n = co32.shape[1]
         if n == 0:
             return np.empty(0, dtype=np.int64)
         L = lib()
         check(L.sdfk_set_device(int(device)), "sdfk_set_device")
-        stride = (n + 63) // 64 * 64
-        d_co = L.sdfk_malloc(3 * stride * 4)
-        if not d_co:
-            raise SdfkError("select: out of device memory")
-        try:
-            for r in range(3):
-                check(L.sdfk_memcpy_h2d(_vp(d_co + 4 * r * stride), _ptr(co32[r]), n * 4), "sdfk_memcpy_h2d")
+        with DeviceCoords(co32, what="select") as d_co:
             # rows: the index at which x or y first changes (3-D grids), else at which x first changes (flat grids)
             row_len, flat = 0, 0
             head = co32[:, :min(n, 1 << 22)]
@@ -468,91 +530,121 @@ class Program:
                     flat = int(co32[2, 0] == 0 and co32[2, row_len - 1] == 0 and co32[2, -1] == 0)
 
             def first(d_scratch, m):
-                check(L.sdfk_eval_device_select(self._h, _vp(d_co), n, stride, row_len, flat, float(threshold), None, 0, m,
-                                                d_scratch, None, mode), "sdfk_eval_device_select")
+                check(L.sdfk_eval_device_select(self._h, _vp(d_co.ptr), n, d_co.stride, row_len, flat, float(threshold), None,
+                                                0, m, d_scratch, None, mode), "sdfk_eval_device_select")
             return self._select(n, first, device, row_len=row_len, mode=mode)
-        finally:
-            L.sdfk_free(_vp(d_co))
 
     def eval_grid_host(self, axes, start=0, count=None, device=0, mode=MODE_AUTO):
         """Field of the grid spanned by three per-axis tables (flat index z fastest), straight to a host array."""
         require_gpu()
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+        ax, tab = axis_args(axes)
         total = ax[0].size * ax[1].size * ax[2].size
         count = total - start if count is None else count
         out = np.empty(count, dtype=np.float32)
-        check(lib().sdfk_eval_grid_host(self._h, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                                        ax[2].size, start, count, _ptr(out), device, mode), "sdfk_eval_grid_host")
+        check(lib().sdfk_eval_grid_host(self._h, *tab, start, count, _ptr(out), device, mode), "sdfk_eval_grid_host")
         return out
 
     def eval_grid_sharded(self, axes, n_shards, devices=None, mode=MODE_AUTO):
         """Whole grid, cut into `n_shards` slabs of whole rows evaluated concurrently on `devices`
         (default: shard d on device d modulo the device count), field returned as one host array."""
         require_gpu()
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+        ax, tab = axis_args(axes)
         out = np.empty(ax[0].size * ax[1].size * ax[2].size, dtype=np.float32)
         dev = None if devices is None else np.ascontiguousarray(devices, dtype=np.int32)
         if dev is not None and dev.size != n_shards:
             raise ValueError("one device per shard")
-        check(lib().sdfk_eval_grid_sharded(self._h, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                                           ax[2].size, n_shards, _ptr(dev) if dev is not None else None, _ptr(out),
-                                           mode), "sdfk_eval_grid_sharded")
+        check(lib().sdfk_eval_grid_sharded(self._h, *tab, n_shards, _ptr(dev) if dev is not None else None, _ptr(out), mode),
+              "sdfk_eval_grid_sharded")
         return out
 
     def eval_grid_sharded_resident(self, axes, n_shards, devices=None, gather_device=0, mode=MODE_AUTO):
         """The same partition, the field reassembled on `gather_device` by device-to-device copies (no host buffer)
         -> DeviceField on that device."""
         require_gpu()
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+        ax, tab = axis_args(axes)
         dev = None if devices is None else np.ascontiguousarray(devices, dtype=np.int32)
         if dev is not None and dev.size != n_shards:
             raise ValueError("one device per shard")
         field = DeviceField(ax[0].size * ax[1].size * ax[2].size, gather_device)
-        check(lib().sdfk_eval_grid_sharded_device(self._h, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                                                  ax[2].size, n_shards, _ptr(dev) if dev is not None else None,
+        check(lib().sdfk_eval_grid_sharded_device(self._h, *tab, n_shards, _ptr(dev) if dev is not None else None,
                                                   int(gather_device), _vp(field.ptr), mode), "sdfk_eval_grid_sharded_device")
         return field
 
     def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            try:
-                _lib.sdfk_program_destroy(h)
-            except Exception:
-                pass
+        _release(self, "_h", "sdfk_program_destroy")
 
 
-class DeviceField:
+def _select(scratch_bytes, count, finish):
+    """Count, allocate the exact result, finish, download: `count(d_scratch, byref(m))` marks and counts the selected
+    points, `finish(m, d_index, d_scratch)` writes their m indices. -> ascending int64 host array."""
+    m = _i64(0)
+    with DeviceBuffer(scratch_bytes, what="select") as scratch:
+        count(scratch.at(), ctypes.byref(m))
+        out = np.empty(m.value, dtype=np.int64)
+        if m.value:
+            with DeviceBuffer(m.value * 8, what="select") as index:
+                finish(m.value, index.at(), scratch.at())
+                index.download(out)
+        return out
+
+
+def extract_mesh(family, shape, level, lead_count, lead_finish, tail=(), timings=None):
+    """Count, allocate the exact result, finish, download of a mesh on a grid of `shape` (3 sizes: isosurface, 2:
+    contour): the entry points `<family>_isosurface` / `_contour2d`, their `_scratch` and `_finish`, called with the
+    leading arguments `lead_count` / `lead_finish` and the trailing ones `tail`. -> (vertices (V, D) float32, faces (F, D)
+    int32, or int64 from 2^31 vertices on). `timings`: a dict that receives device-event milliseconds of count / emit /
+    copy."""
+    L = lib()
+    dims = len(shape)
+    name = family + ("_isosurface" if dims == 3 else "_contour2d")
+    lv = _c.c_float(level)
+    nv, nf = _i64(0), _i64(0)
+    timer = Timer(timings)
+    with contextlib.ExitStack() as stack:
+        def alloc(nbytes):
+            return stack.enter_context(DeviceBuffer(nbytes, what="mesh"))
+        timer.mark("start")
+        scratch = alloc(getattr(L, name + "_scratch")(*shape))
+        check(getattr(L, name)(*lead_count, lv, ctypes.byref(nv), ctypes.byref(nf), scratch.at(), None, *tail), name)
+        timer.mark("count")
+        V, F = nv.value, nf.value
+        wide = V > 0x7fffffff
+        d_v = alloc(V * dims * 4)
+        d_f = alloc(F * dims * (8 if wide else 4))
+        check(getattr(L, name + "_finish")(*lead_finish, lv, V, F, d_v.at(), V, d_f.at(), F, 8 if wide else 4, scratch.at(),
+                                           None, *tail), name + "_finish")
+        timer.mark("emit")
+        verts = d_v.download(np.empty((V, dims), dtype=np.float32))
+        faces = d_f.download(np.empty((F, dims), dtype=np.int64 if wide else np.int32))
+        timer.mark("copy")
+        timer.finish()
+        return verts, faces
+
+
+class DeviceField(DeviceBuffer):
     """An (N,) float32 scalar field resident in HBM (what `create_resident` returns): the consumers of the field run
     on it without the field ever crossing PCIe. Owns its device memory; `free()` (or garbage collection) releases it."""
 
     def __init__(self, n, device=0):
         require_gpu()
-        self.n, self.device = int(n), int(device)
-        check(lib().sdfk_set_device(self.device), "sdfk_set_device")
-        self.ptr = lib().sdfk_malloc(max(self.n, 1) * 4)
-        if not self.ptr:
-            raise SdfkError("DeviceField: out of device memory: " + last_error())
+        self.n = int(n)
+        DeviceBuffer.__init__(self, self.n * 4, device)
 
     @classmethod
     def from_host(cls, field, device=0):
         host = np.ascontiguousarray(field, dtype=np.float32).ravel()
         self = cls(host.size, device)
-        if host.size:
-            check(lib().sdfk_memcpy_h2d(_vp(self.ptr), _ptr(host), host.size * 4), "sdfk_memcpy_h2d")
-        return self
+        return self._filled(self.upload, host)
 
-    def _live(self):
-        if not self.ptr:
-            raise SdfkError("DeviceField has been freed")
-        check(lib().sdfk_set_device(self.device), "sdfk_set_device")
+    @classmethod
+    def from_device(cls, device_ptr, n, device=0):
+        """A copy of the n floats at the device pointer (int) `device_ptr`."""
+        self = cls(n, device)
+        return self._filled(self.copy_from, device_ptr, self.n * 4)
 
     def numpy(self):
         self._live()
-        out = np.empty(self.n, dtype=np.float32)
-        if self.n:
-            check(lib().sdfk_memcpy_d2h(_ptr(out), _vp(self.ptr), self.n * 4), "sdfk_memcpy_d2h")
-        return out
+        return self.download(np.empty(self.n, dtype=np.float32))
 
     def count(self, threshold=0.0):
         """Number of points with field <= threshold."""
@@ -567,27 +659,13 @@ class DeviceField:
         only the indices cross PCIe."""
         self._live()
         L = lib()
-        m = _i64(0)
-        d_scratch = L.sdfk_malloc(L.sdfk_field_select_scratch(self.n))
-        d_index = None
-        try:
-            if not d_scratch:
-                raise SdfkError("select: out of device memory")
-            check(L.sdfk_field_select(_vp(self.ptr), self.n, float(threshold), None, 0, ctypes.byref(m), _vp(d_scratch),
-                                      None), "sdfk_field_select")
-            out = np.empty(m.value, dtype=np.int64)
-            if m.value:
-                d_index = L.sdfk_malloc(m.value * 8)
-                if not d_index:
-                    raise SdfkError("select: out of device memory")
-                check(L.sdfk_field_select_finish(self.n, m.value, _vp(d_index), m.value, _vp(d_scratch), None),
-                      "sdfk_field_select_finish")
-                check(L.sdfk_memcpy_d2h(_ptr(out), _vp(d_index), out.size * 8), "sdfk_memcpy_d2h")
-            return out
-        finally:
-            for d in (d_scratch, d_index):
-                if d:
-                    L.sdfk_free(_vp(d))
+
+        def count(d_scratch, m):
+            check(L.sdfk_field_select(_vp(self.ptr), self.n, float(threshold), None, 0, m, d_scratch, None), "sdfk_field_select")
+
+        def finish(m, d_index, d_scratch):
+            check(L.sdfk_field_select_finish(self.n, m, d_index, m, d_scratch, None), "sdfk_field_select_finish")
+        return _select(L.sdfk_field_select_scratch(self.n), count, finish)
 
     def gradient(self, shape, normalize=True):
         """numpy.gradient (unit spacing) of the field reshaped to `shape` (1 to 3 axes), every vector normalised
@@ -599,20 +677,10 @@ class DeviceField:
         if min(shape) < 2:
             raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.")
         dims = (1,) * (3 - len(shape)) + shape
-        L = lib()
-        stride = (self.n + 63) // 64 * 64
-        d_vec = L.sdfk_malloc(len(shape) * stride * 4)
-        if not d_vec:
-            raise SdfkError("gradient: out of device memory")
-        try:
-            check(L.sdfk_field_gradient(_vp(self.ptr), dims[0], dims[1], dims[2], len(shape), 1 if normalize else 0,
-                                        _vp(d_vec), stride, None), "sdfk_field_gradient")
-            out = np.empty((len(shape), self.n), dtype=np.float32)
-            for r in range(len(shape)):
-                check(L.sdfk_memcpy_d2h(_ptr(out[r]), _vp(d_vec + 4 * r * stride), self.n * 4), "sdfk_memcpy_d2h")
-            return out
-        finally:
-            L.sdfk_free(_vp(d_vec))
+        with DeviceRows(len(shape), self.n, what="gradient") as vec:
+            check(lib().sdfk_field_gradient(_vp(self.ptr), dims[0], dims[1], dims[2], len(shape), 1 if normalize else 0,
+                                            vec.at(), vec.stride, None), "sdfk_field_gradient")
+            return vec.download_rows()
 
     def gradient_resident(self, shape, normalize=True):
         """gradient() of a 3-D field, left on the device as a DeviceVectorField."""
@@ -627,31 +695,15 @@ class DeviceField:
                                         out.stride, None), "sdfk_field_gradient")
         return out
 
-    def free(self):
-        p, self.ptr = getattr(self, "ptr", None), None
-        if p and _lib is not None:
-            _lib.sdfk_free(_vp(p))
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DeviceVectorField:
+class DeviceVectorField(DeviceRows):
     """A (3, N) float32 vector field resident in HBM (what `VectorField.create_resident` returns): three rows of
     `stride` floats. Usable as the input, a second field or the revolution coordinates of another vector-field chain
     without crossing PCIe. Owns its device memory."""
 
     def __init__(self, n, device=0):
         require_gpu()
-        self.n, self.device = int(n), int(device)
-        self.stride = (self.n + 63) // 64 * 64
-        check(lib().sdfk_set_device(self.device), "sdfk_set_device")
-        self.ptr = lib().sdfk_malloc(max(self.stride, 64) * 3 * 4)
-        if not self.ptr:
-            raise SdfkError("DeviceVectorField: out of device memory: " + last_error())
+        DeviceRows.__init__(self, 3, n, device)
 
     shape = property(lambda self: (3, self.n))
 
@@ -661,34 +713,44 @@ class DeviceVectorField:
         if host.ndim != 2 or host.shape[0] != 3:
             raise ValueError("a vector field has shape (3, N); got %r" % (host.shape,))
         self = cls(host.shape[1], device)
-        for r in range(3):
-            if self.n:
-                check(lib().sdfk_memcpy_h2d(_vp(self.ptr + 4 * r * self.stride), _ptr(host[r]), self.n * 4), "sdfk_memcpy_h2d")
-        return self
-
-    def row_ptr(self, r):
-        if not self.ptr:
-            raise SdfkError("DeviceVectorField has been freed")
-        return self.ptr + 4 * r * self.stride
+        return self._filled(self.upload_rows, host)
 
     def numpy(self):
-        check(lib().sdfk_set_device(self.device), "sdfk_set_device")
-        out = np.empty((3, self.n), dtype=np.float32)
-        for r in range(3):
-            if self.n:
-                check(lib().sdfk_memcpy_d2h(_ptr(out[r]), _vp(self.row_ptr(r)), self.n * 4), "sdfk_memcpy_d2h")
-        return out
+        self._live()
+        return self.download_rows()
+
+
+class DeviceCoords:
+    """(3, N) coordinates on the device (`ptr`, `stride`, `n`): borrowed from a DeviceVectorField, or owned — points
+    [first, first + count) of the grid the per-axis tables `axes` span, filled on the device, or a host array, uploaded
+    as float32 (as create() does). free(), or leaving a `with` block, releases what is owned."""
+
+    def __init__(self, co, axes=None, first=0, count=None, device=None, what="coordinates"):
+        self.owned = None
+        if isinstance(co, DeviceVectorField):
+            self.ptr, self.stride, self.n = co.row_ptr(0), co.stride, co.n
+            return
+        if axes is not None:
+            n = int(np.prod([np.asarray(a).size for a in axes])) - first if count is None else count
+        else:
+            host = host_coords(co, np.float32)
+            n = host.shape[1]
+        rows = DeviceRows(3, n, device, what)
+        if axes is not None:
+            rows._filled(grid_fill, rows.ptr, rows.stride, axes, first, n)
+        else:
+            rows._filled(rows.upload_rows, host)
+        self.owned, self.ptr, self.stride, self.n = rows, rows.ptr, rows.stride, n
 
     def free(self):
-        p, self.ptr = getattr(self, "ptr", None), None
-        if p and _lib is not None:
-            _lib.sdfk_free(_vp(p))
+        if self.owned is not None:
+            self.owned.free()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
 
 def linspace_f32(lo, hi, n):
@@ -718,9 +780,8 @@ def point_tree(points32, leaf, with_order=False):
 
 
 def grid_fill(d_co, row_stride, axes, start, count, stream=None):
-    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
-    check(lib().sdfk_grid_fill(_vp(d_co), row_stride, _ptr(ax[0]), ax[0].size, _ptr(ax[1]), ax[1].size, _ptr(ax[2]),
-                               ax[2].size, start, count, _vp(stream or 0)), "sdfk_grid_fill")
+    _, tab = axis_args(axes)
+    check(lib().sdfk_grid_fill(_vp(d_co), row_stride, *tab, start, count, _vp(stream or 0)), "sdfk_grid_fill")
 
 
 class Event:
@@ -738,9 +799,25 @@ class Event:
         return ms.value
 
     def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            try:
-                _lib.sdfk_event_destroy(h)
-            except Exception:
-                pass
+        _release(self, "_h", "sdfk_event_destroy")
+
+
+class Timer:
+    """Device-event milliseconds between consecutive mark()s, added to `timings[name]` under the name of the later
+    mark. timings=None: no event is created."""
+
+    def __init__(self, timings):
+        self.timings = timings
+        self.events = []
+
+    def mark(self, name):
+        if self.timings is not None:
+            ev = Event()
+            ev.record()
+            self.events.append((name, ev))
+
+    def finish(self):
+        if self.timings is None:
+            return
+        for (_, a), (name, b) in zip(self.events, self.events[1:]):
+            self.timings[name] = self.timings.get(name, 0.0) + a.elapsed_ms(b)

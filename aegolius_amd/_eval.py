@@ -4,6 +4,7 @@ There is exactly one evaluation path — libsdfk.so on an MI355X. No NumPy evalu
 package; without the extension or without a GPU these functions raise.
 """
 import collections
+import contextlib
 import threading
 
 import numpy as np
@@ -43,6 +44,13 @@ def program_for(lowered):
     return prog
 
 
+def device_coords(co, what="coordinates"):
+    """_engine.DeviceCoords of what create() accepts — a generate_grid array is filled on the device from its axis
+    tables, any other host array uploaded as fp32 — or of a DeviceVectorField."""
+    axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
+    return _engine.DeviceCoords(co, axes, what=what)
+
+
 def _run(lowered, co, resident=False):
     axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
     if resident:
@@ -65,12 +73,7 @@ def _run_resident(lowered, co, axes):
         prog.eval_grid(axes, 0, n, field.ptr, mode=config.mode)
         _engine.check(_engine.lib().sdfk_sync(None), "sdfk_sync")
         return field
-    co = np.asarray(co)
-    if co.ndim != 2 or co.shape[0] != 3:
-        raise ValueError("coordinates must have shape (3, N); got %r" % (co.shape,))
-    if co.dtype not in (np.float32, np.float64):
-        co = co.astype(np.float64)
-    co = np.ascontiguousarray(co)
+    co = _engine.host_coords(co)
     n = co.shape[1]
     field = _engine.DeviceField(n, config.device)
     _engine.check(_engine.lib().sdfk_eval_host_resident(prog.handle, _engine._ptr(co), 0 if co.dtype == np.float32 else 1, n,
@@ -155,29 +158,22 @@ def apply_fields(fields, emit):
     device = fields[0].device if resident else config.device
     _engine.check(lib.sdfk_set_device(device), "sdfk_set_device")
     vp = _engine._vp
-    stride = (n + 63) // 64 * 64
-    rows = max(len(fields), 3)                       # the rows double as the (never read) coordinate array
-    d_aux = lib.sdfk_malloc(rows * stride * 4)
-    out = _engine.DeviceField(n, device)
-    if not d_aux:
-        raise _engine.SdfkError("apply_fields: out of device memory")
-    try:
+    # the rows double as the (never read) coordinate array
+    with contextlib.ExitStack() as on_error, _engine.DeviceRows(max(len(fields), 3), n, what="apply_fields") as aux:
+        out = on_error.enter_context(_engine.DeviceField(n, device))
         for k, f in enumerate(fields):
-            row = d_aux + 4 * k * stride
             if host[k] is None:
                 f._live()
-                _engine.check(lib.sdfk_memcpy_d2d(vp(row), vp(f.ptr), n * 4), "d2d")
+                aux.copy_from(f.ptr, n * 4, aux.offset(k))
             else:
-                _engine.check(lib.sdfk_memcpy_h2d(vp(row), _engine._ptr(host[k]), n * 4), "h2d")
-        _engine.check(lib.sdfk_eval_device_aux(program_for(lowered).handle, vp(d_aux), n, stride, vp(d_aux), len(fields), stride,
-                                               vp(out.ptr), None, config.mode), "sdfk_eval_device_aux")
+                aux.upload(host[k], aux.offset(k))
+        _engine.check(lib.sdfk_eval_device_aux(program_for(lowered).handle, aux.at(), n, aux.stride, aux.at(), len(fields),
+                                               aux.stride, vp(out.ptr), None, config.mode), "sdfk_eval_device_aux")
         _engine.check(lib.sdfk_sync(None), "sdfk_sync")
-    finally:
-        lib.sdfk_free(vp(d_aux))
-    if resident:
-        return out
-    res = out.numpy()
-    out.free()
+        if resident:
+            on_error.pop_all()
+            return out
+        res = out.numpy()
     if config.output_dtype is not np.float32:
         res = res.astype(config.output_dtype)
     return res.reshape(shape)
@@ -203,19 +199,12 @@ def apply_grid_op(name, u, args):
     if arr.ndim not in (2, 3):
         raise ValueError("the field must be a 2-D or 3-D grid; got shape %r" % (arr.shape,))
     n = arr.size
-    field = _engine.DeviceField.from_host(arr, config.device)
-    d_scratch = lib.sdfk_malloc(max(n, 1) * 4)
-    try:
-        if not d_scratch:
-            raise _engine.SdfkError("out of device memory")
+    with _engine.DeviceField.from_host(arr, config.device) as field, \
+            _engine.DeviceBuffer(n * 4, what="apply_grid_op") as scratch:
         node = ModSDF(name, dict(args, co_resolution=arr.shape), None)
-        _apply_grid_op(lib, node, None, field.ptr, n, None, None, None, d_scratch, shape=arr.shape)
+        _apply_grid_op(lib, node, None, field.ptr, n, None, None, None, scratch.ptr, shape=arr.shape)
         _engine.check(lib.sdfk_sync(None), "sdfk_sync")
         out = field.numpy()
-    finally:
-        if d_scratch:
-            lib.sdfk_free(_engine._vp(d_scratch))
-        field.free()
     if config.output_dtype is not np.float32:
         out = out.astype(config.output_dtype)
     return out.reshape(arr.shape)
@@ -314,23 +303,15 @@ def _apply_grid_op(lib, node, key, d_field, n, lower, fields, points4, d_scratch
 def _eval_few(lib, lowered, points, n_aux):
     """A program on a handful of points (fields of earlier stages, if it reads any, are dead code there: zeros)."""
     m = int(points.shape[1])
-    vp = _engine._vp
     host = np.zeros((3 + max(n_aux, 1) + 1, 64), dtype=np.float32)
     host[:3, :m] = points
-    d = lib.sdfk_malloc(host.nbytes)
-    if not d:
-        raise _engine.SdfkError("staged evaluation: out of device memory")
-    try:
-        _engine.check(lib.sdfk_memcpy_h2d(vp(d), _engine._ptr(host), host.nbytes), "h2d")
-        d_aux, d_out = d + 4 * 3 * 64, d + 4 * (3 + max(n_aux, 1)) * 64
-        _engine.check(lib.sdfk_eval_device_aux(program_for(lowered).handle, vp(d), m, 64, vp(d_aux), max(n_aux, 1), 64,
-                                               vp(d_out), None, config.mode), "sdfk_eval_device_aux")
+    with _engine.DeviceRows(host.shape[0], 64, what="staged evaluation") as d:
+        d.upload(host)
+        d_out = d.row(host.shape[0] - 1)
+        _engine.check(lib.sdfk_eval_device_aux(program_for(lowered).handle, d.at(), m, 64, d.row(3), max(n_aux, 1), 64, d_out,
+                                               None, config.mode), "sdfk_eval_device_aux")
         _engine.check(lib.sdfk_sync(None), "sdfk_sync")
-        out = np.empty(m, dtype=np.float32)
-        _engine.check(lib.sdfk_memcpy_d2h(_engine._ptr(out), vp(d_out), m * 4), "d2h")
-        return out
-    finally:
-        lib.sdfk_free(vp(d))
+        return d.download(np.empty(m, dtype=np.float32), d.offset(host.shape[0] - 1))
 
 
 def _edge_detection_is_outermost(expr):
@@ -348,26 +329,20 @@ def _edge_detection_is_outermost(expr):
             return None
 
 
-def _run_host_op(lib, node, key, params, lowered, k, n, stride, d_aux, d_out, run_program, lower, known):
+def _run_host_op(node, key, params, lowered, k, aux, out, run_program, lower, known):
     """custom_post_process / custom_modification / an opaque SDF callable: user code on the host between two GPU
     stages. The field (or the coordinates the closure is handed) comes back over PCIe, the result goes up as
     auxiliary field k. Functional completeness, not a fast path."""
-    vp = _engine._vp
-    row = d_aux + 4 * k * stride
+    n = aux.n
     buf = np.empty(n, dtype=np.float32)
-
-    def fetch(d_src):
-        _engine.check(lib.sdfk_memcpy_d2h(_engine._ptr(buf), vp(d_src), n * 4), "d2h")
-        return buf.astype(np.float64)
-
     if node.name == "custom_post_process":
-        run_program(lowered, row, k)
-        result = node.args["function"](fetch(row), *node.args["parameters"])
+        run_program(lowered, aux.row_ptr(k), k)
+        result = node.args["function"](aux.download(buf, aux.offset(k)).astype(np.float64), *node.args["parameters"])
     else:
         co_here = np.empty((3, n), dtype=np.float64)
         for axis in range(3):
-            run_program(lower(fields=known, stop_at=key, probe_axis=axis), d_out, k)
-            co_here[axis] = fetch(d_out)
+            run_program(lower(fields=known, stop_at=key, probe_axis=axis), out.ptr, k)
+            co_here[axis] = out.download(buf)
         if node.name == "custom_modification":
             inner = node.inner
 
@@ -379,8 +354,7 @@ def _run_host_op(lib, node, key, params, lowered, k, n, stride, d_aux, d_out, ru
     result = np.asarray(result, dtype=np.float32)
     if result.shape != (n,):
         raise ValueError("%s returned an array of shape %r, expected (%d,)" % (node.name, result.shape, n))
-    result = np.ascontiguousarray(result)
-    _engine.check(lib.sdfk_memcpy_h2d(vp(row), _engine._ptr(result), n * 4), "h2d")
+    aux.upload(result, aux.offset(k))
 
 
 def _run_staged(lower, co, root=None, resident=False):
@@ -391,32 +365,22 @@ def _run_staged(lower, co, root=None, resident=False):
     n = int(co.shape[1])
     axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
     vp = _engine._vp
-    stride = (n + 63) // 64 * 64
-    d_aux = lib.sdfk_malloc(len(stages) * stride * 4)
-    d_out = lib.sdfk_malloc(stride * 4)
-    d_co = None
-    if not d_aux or not d_out:
-        raise _engine.SdfkError("staged evaluation: out of device memory")
-    try:
+    with contextlib.ExitStack() as stack:
+        aux = stack.enter_context(_engine.DeviceRows(len(stages), n, what="staged evaluation"))
+        d_out = stack.enter_context(_engine.DeviceRows(1, n, what="staged evaluation"))
+        stride = aux.stride
         if axes is None:
-            host = np.ascontiguousarray(co, dtype=np.float32)
-            if host.shape[0] != 3:
-                raise ValueError("coordinates must have shape (3, N)")
-            d_co = lib.sdfk_malloc(3 * stride * 4)
-            if not d_co:
-                raise _engine.SdfkError("staged evaluation: out of device memory")
-            for r in range(3):
-                _engine.check(lib.sdfk_memcpy_h2d(vp(d_co + 4 * r * stride), _engine._ptr(host[r]), n * 4), "h2d")
-        ax = None if axes is None else [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+            coords = stack.enter_context(_engine.DeviceCoords(co, what="staged evaluation"))
+        else:
+            _, tab = _engine.axis_args(axes)
 
         def run_program(lowered, d_dst, n_aux):
             prog = program_for(lowered)
-            if ax is not None:
-                _engine.check(lib.sdfk_eval_grid_aux(prog.handle, _engine._ptr(ax[0]), ax[0].size, _engine._ptr(ax[1]),
-                                                     ax[1].size, _engine._ptr(ax[2]), ax[2].size, 0, n, vp(d_aux), n_aux,
-                                                     stride, vp(d_dst), None, config.mode), "sdfk_eval_grid_aux")
+            if axes is not None:
+                _engine.check(lib.sdfk_eval_grid_aux(prog.handle, *tab, 0, n, aux.at(), n_aux, stride, vp(d_dst), None,
+                                                     config.mode), "sdfk_eval_grid_aux")
             else:
-                _engine.check(lib.sdfk_eval_device_aux(prog.handle, vp(d_co), n, stride, vp(d_aux), n_aux, stride,
+                _engine.check(lib.sdfk_eval_device_aux(prog.handle, vp(coords.ptr), n, coords.stride, aux.at(), n_aux, stride,
                                                        vp(d_dst), None, config.mode), "sdfk_eval_device_aux")
                 _engine.check(lib.sdfk_sync(None), "sdfk_sync")
 
@@ -426,28 +390,21 @@ def _run_staged(lower, co, root=None, resident=False):
         from ._mods import HOST_OPS
         for k, (lowered, node, key, params) in enumerate(stages):
             if node.name in HOST_OPS:
-                _run_host_op(lib, node, key, params, lowered, k, n, stride, d_aux, d_out, run_program, lower, known)
+                _run_host_op(node, key, params, lowered, k, aux, d_out, run_program, lower, known)
                 known[key] = k
                 continue
-            run_program(lowered, d_aux + 4 * k * stride, k)
+            run_program(lowered, aux.row_ptr(k), k)
             if node.name in ("signed", "signed_old") and points4 is None:
                 shape = _grid_shape(n, node.args["co_resolution"])
                 if len(shape) == 3:
                     idx = [0, shape[1] * shape[2], shape[2], 1]
                     points4 = np.stack([np.asarray(co[r])[idx] for r in range(3)]).astype(np.float64)
-            _apply_grid_op(lib, node, key, d_aux + 4 * k * stride, n, lower, known, points4, d_out)   # d_out doubles as scratch
+            _apply_grid_op(lib, node, key, aux.row_ptr(k), n, lower, known, points4, d_out.ptr)   # d_out doubles as scratch
             known[key] = k
-        run_program(final, d_out, len(stages))
+        run_program(final, d_out.ptr, len(stages))
         if resident:
-            field = _engine.DeviceField(n, config.device)
-            _engine.check(lib.sdfk_memcpy_d2d(vp(field.ptr), vp(d_out), n * 4), "d2d")
-            return field
-        out = np.empty(n, dtype=np.float32)
-        _engine.check(lib.sdfk_memcpy_d2h(_engine._ptr(out), vp(d_out), n * 4), "d2h")
-    finally:
-        for d in (d_aux, d_out, d_co):
-            if d:
-                lib.sdfk_free(vp(d))
+            return _engine.DeviceField.from_device(d_out.ptr, n, config.device)
+        out = d_out.download(np.empty(n, dtype=np.float32))
     if config.output_dtype is not np.float32:
         out = out.astype(config.output_dtype)
     edge = _edge_detection_is_outermost(root) if root is not None else None
@@ -497,7 +454,7 @@ def evaluate_slab_staged(lower, axes, plane0, planes, out_ptr, comm=None):
     _engine.require_gpu()
     lib = _engine.lib()
     vp = _engine._vp
-    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
+    ax, tab = _engine.axis_args(axes)
     n0, n1, n2 = (int(a.size) for a in ax)
     flat2d = n2 == 1
     grid_shape = (n0, n1) if flat2d else (n0, n1, n2)
@@ -507,20 +464,16 @@ def evaluate_slab_staged(lower, axes, plane0, planes, out_ptr, comm=None):
     e0, e1 = max(0, plane0 - halo), min(n0, plane0 + planes + halo)
     n = (e1 - e0) * plane
     ext_shape = (e1 - e0, n1) if flat2d else (e1 - e0, n1, n2)
-    stride = (n + 63) // 64 * 64
-    d_aux = lib.sdfk_malloc(max(1, len(stages)) * stride * 4)
-    d_tmp = lib.sdfk_malloc(stride * 4)
-    d_mask = None
-    if not d_aux or not d_tmp:
-        raise _engine.SdfkError("staged slab evaluation: out of device memory")
-    try:
+    with _engine.DeviceRows(max(1, len(stages)), n, what="staged slab evaluation") as aux, \
+            _engine.DeviceRows(1, n, what="staged slab evaluation") as tmp:
+        stride = aux.stride
+
         def run_program(lowered, d_dst, n_aux):
-            _engine.check(lib.sdfk_eval_grid_aux(program_for(lowered).handle, _engine._ptr(ax[0]), n0, _engine._ptr(ax[1]), n1,
-                                                 _engine._ptr(ax[2]), n2, e0 * plane, n, vp(d_aux), n_aux, stride, vp(d_dst),
-                                                 None, config.mode), "sdfk_eval_grid_aux")
+            _engine.check(lib.sdfk_eval_grid_aux(program_for(lowered).handle, *tab, e0 * plane, n, aux.at(), n_aux, stride,
+                                                 vp(d_dst), None, config.mode), "sdfk_eval_grid_aux")
         known = {}
         for k, (lowered, node, key, _params) in enumerate(stages):
-            row = d_aux + 4 * k * stride
+            row = aux.row_ptr(k)
             run_program(lowered, row, k)
             if node.name in ("signed", "signed_old"):
                 if flat2d:
@@ -545,25 +498,18 @@ def evaluate_slab_staged(lower, axes, plane0, planes, out_ptr, comm=None):
                         vals = _eval_few(lib, lower(fields=known, stop_at=key, probe_axis=axis), points4, len(known))
                         seps.append(abs(float(vals[1 + axis]) - float(vals[0])))
                     sep = float(np.float32(min(seps)))
-                    d_mask = lib.sdfk_malloc(max(1, planes * plane))
-                    if not d_mask:
-                        raise _engine.SdfkError("staged slab evaluation: out of device memory")
-                    _engine.check(lib.sdfk_grid_boundary_mask(vp(own), planes * plane, sep, vp(d_mask), None), "sdfk_grid_boundary_mask")
-                    _engine.check(lib.sdfk_sync(None), "sdfk_sync")
-                    d_full = comm.allgather_bytes(d_mask, plane0 * plane, planes * plane, n0 * plane)
-                    _engine.check(lib.sdfk_grid_signed_slab(vp(row), e0, e1 - e0, vp(d_full), n0, n1, n2,
-                                                            0 if node.name == "signed_old" else 1, None, None),
-                                  "sdfk_grid_signed_slab")
-                    lib.sdfk_free(vp(d_mask))
-                    d_mask = None
+                    with _engine.DeviceBuffer(planes * plane, what="staged slab evaluation") as mask:
+                        _engine.check(lib.sdfk_grid_boundary_mask(vp(own), planes * plane, sep, mask.at(), None),
+                                      "sdfk_grid_boundary_mask")
+                        _engine.check(lib.sdfk_sync(None), "sdfk_sync")
+                        d_full = comm.allgather_bytes(mask.ptr, plane0 * plane, planes * plane, n0 * plane)
+                        _engine.check(lib.sdfk_grid_signed_slab(vp(row), e0, e1 - e0, vp(d_full), n0, n1, n2,
+                                                                0 if node.name == "signed_old" else 1, None, None),
+                                      "sdfk_grid_signed_slab")
             else:
-                _apply_grid_op(lib, node, key, row, n, lower, known, None, d_tmp, shape=ext_shape)
+                _apply_grid_op(lib, node, key, row, n, lower, known, None, tmp.ptr, shape=ext_shape)
             known[key] = k
-        run_program(final, d_tmp, len(stages))
+        run_program(final, tmp.ptr, len(stages))
         # hipMemcpy device-to-device through the plumbing entry point (any direction works for device pointers)
-        _engine.check(lib.sdfk_memcpy_d2d(vp(out_ptr), vp(d_tmp + 4 * (plane0 - e0) * plane), planes * plane * 4), "d2d")
-    finally:
-        lib.sdfk_free(vp(d_aux))
-        lib.sdfk_free(vp(d_tmp))
-        if d_mask:
-            lib.sdfk_free(vp(d_mask))
+        nbytes = planes * plane * 4
+        _engine.check(lib.sdfk_memcpy_d2d(vp(out_ptr), tmp.at(4 * (plane0 - e0) * plane, nbytes), nbytes), "d2d")

@@ -5,6 +5,7 @@ the occupied region plane by plane. Here the inputs are checked and the bin edge
 does (same exceptions, `numpy.linspace` edges); the occupancy grid is one byte per voxel in HBM, binned, extended and
 widened there. Only the edge tables, the cloud, rx + ry + rz plane flags and the result cross PCIe.
 """
+import contextlib
 import ctypes
 import operator
 
@@ -68,24 +69,6 @@ def _plane_range(flags, sign):
     return src, src + 1, flags.size
 
 
-class _Timer:
-    def __init__(self, timings):
-        self.timings = timings
-        self.events = []
-
-    def mark(self, name):
-        if self.timings is not None:
-            ev = _engine.Event()
-            ev.record()
-            self.events.append((name, ev))
-
-    def finish(self):
-        if self.timings is None:
-            return
-        for (_, a), (name, b) in zip(self.events, self.events[1:]):
-            self.timings[name] = self.timings.get(name, 0.0) + a.elapsed_ms(b)
-
-
 def to_image(cloud, co_size, co_resolution, extend, resident=False, device=0, transfer=None, timings=None):
     """The reference's Points.to_image grid: (rx, ry, rz) float64 on the host, or (resident=True) a DeviceField of
     rx ry rz float32 0 / 1 values in C order. `transfer`: "bytes" or "f64" (see DEFAULT_TRANSFER). `timings`: a dict
@@ -101,33 +84,27 @@ def to_image(cloud, co_size, co_resolution, extend, resident=False, device=0, tr
     nvox = rx * ry * rz
     n = sample.shape[1]
     table = np.ascontiguousarray(np.concatenate(edges), dtype=np.float64)
-    bufs = []
-
-    def alloc(nbytes):
-        p = L.sdfk_malloc(max(int(nbytes), 1))
-        if not p:
-            raise _engine.SdfkError("to_image: out of device memory (%d bytes)" % nbytes)
-        bufs.append(p)
-        return ctypes.c_void_p(p)
-
-    timer = _Timer(timings)
-    try:
-        d_grid = alloc(nvox)
+    timer = _engine.Timer(timings)
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        def alloc(nbytes):
+            return stack.enter_context(_engine.DeviceBuffer(nbytes, what="to_image"))
+        grid = alloc(nvox)
+        d_grid = grid.at()
         d_edges = alloc(table.nbytes)
-        _engine.check(L.sdfk_memcpy_h2d(d_edges, _engine._ptr(table), table.nbytes), "sdfk_memcpy_h2d")
+        d_edges.upload(table)
         d_cloud = None
         if n:
-            d_cloud = alloc(sample.nbytes)
-            _engine.check(L.sdfk_memcpy_h2d(d_cloud, _engine._ptr(sample), sample.nbytes), "sdfk_memcpy_h2d")
+            cloud_buf = alloc(sample.nbytes)
+            cloud_buf.upload(sample)
+            d_cloud = cloud_buf.at()
         timer.mark("start")
-        _engine.check(L.sdfk_points_bin(d_cloud, n, n, d_edges, rx, ry, rz, d_grid, None), "sdfk_points_bin")
+        _engine.check(L.sdfk_points_bin(d_cloud, n, n, d_edges.at(), rx, ry, rz, d_grid, None), "sdfk_points_bin")
         timer.mark("bin")
         steps = [(ex[0], _AXIS[ex[1]]) for ex in entries if ex in ("-X", "+X", "-Y", "+Y", "-Z", "+Z")]
         if steps:
             d_flags = alloc(rx + ry + rz)
-            _engine.check(L.sdfk_points_extent(d_grid, rx, ry, rz, d_flags, None), "sdfk_points_extent")
-            flags = np.empty(rx + ry + rz, dtype=np.uint8)
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(flags), d_flags, flags.nbytes), "sdfk_memcpy_d2h")
+            _engine.check(L.sdfk_points_extent(d_grid, rx, ry, rz, d_flags.at(), None), "sdfk_points_extent")
+            flags = d_flags.download(np.empty(rx + ry + rz, dtype=np.uint8))
             timer.mark("extent")
             per_axis = [flags[:rx], flags[rx:rx + ry], flags[rx + ry:]]
             for sign, axis in steps:
@@ -137,24 +114,20 @@ def to_image(cloud, co_size, co_resolution, extend, resident=False, device=0, tr
                     per_axis[axis][lo:hi] = 1          # a copied plane is occupied; the other axes' flags stay
             timer.mark("fill")
         if resident:
-            field = _engine.DeviceField(nvox, device)
+            field = on_error.enter_context(_engine.DeviceField(nvox, device))
             _engine.check(L.sdfk_points_widen(d_grid, nvox, 1, ctypes.c_void_p(field.ptr), None), "sdfk_points_widen")
             _engine.check(L.sdfk_sync(None), "sdfk_sync")
             timer.mark("transfer")
             timer.finish()
+            on_error.pop_all()
             return field
         out = np.empty(res, dtype=np.float64)
         if transfer == "f64":
             d_wide = alloc(nvox * 8)
-            _engine.check(L.sdfk_points_widen(d_grid, nvox, 0, d_wide, None), "sdfk_points_widen")
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(out), d_wide, out.nbytes), "sdfk_memcpy_d2h")
+            _engine.check(L.sdfk_points_widen(d_grid, nvox, 0, d_wide.at(), None), "sdfk_points_widen")
+            d_wide.download(out)
         else:
-            occ = np.empty(res, dtype=np.uint8)
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(occ), d_grid, occ.nbytes), "sdfk_memcpy_d2h")
-            np.copyto(out, occ, casting="safe")
+            np.copyto(out, grid.download(np.empty(res, dtype=np.uint8)), casting="safe")
         timer.mark("transfer")
         timer.finish()
         return out
-    finally:
-        for p in bufs:
-            L.sdfk_free(ctypes.c_void_p(p))

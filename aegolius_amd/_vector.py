@@ -7,6 +7,7 @@ to a program for `sdfk_vec_eval_host` (include/sdfk.h): numbers and 3-vectors be
 reference would broadcast become rows of a `streams` array. There is no NumPy evaluation of a chain here; without
 the extension or a GPU the call raises.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -356,44 +357,26 @@ def _run_device(b, p_arr, grid_axes, out_kind, config, resident, slab=None):
     first, n = slab if slab is not None else (0, b.n)
     _engine.check(lib.sdfk_set_device(config.device), "sdfk_set_device")
     prog = (VecInstr * len(b.instr))(*b.instr)
-    stride = (n + 63) // 64 * 64
-    own_p = None
-    d_streams = None
-    result = _engine.DeviceVectorField(n, config.device) if out_kind == 0 else _engine.DeviceField(stride, config.device)
-    try:
-        if isinstance(p_arr, _engine.DeviceVectorField):
-            d_p, p_stride = p_arr.ptr, p_arr.stride
-        else:
-            own_p = _engine.DeviceVectorField(n, config.device)
-            d_p, p_stride = own_p.ptr, own_p.stride
-            if grid_axes is not None:
-                _engine.grid_fill(d_p, p_stride, grid_axes, first, n)
-            else:
-                host = np.ascontiguousarray(p_arr, dtype=np.float32)
-                for r in range(3):
-                    if n:
-                        _engine.check(lib.sdfk_memcpy_h2d(vp(own_p.row_ptr(r)), _engine._ptr(host[r]), n * 4), "h2d")
+    stride = _engine.row_stride(n)
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        result = on_error.enter_context(_engine.DeviceVectorField(n, config.device) if out_kind == 0
+                                        else _engine.DeviceField(stride, config.device))
+        p = stack.enter_context(_engine.DeviceCoords(p_arr, grid_axes, first, n, config.device, "vector chain"))
+        streams = None
         if b.rows:
-            d_streams = lib.sdfk_malloc(len(b.rows) * stride * 4)
-            if not d_streams:
-                raise _engine.SdfkError("vector chain: out of device memory")
+            streams = stack.enter_context(_engine.DeviceRows(len(b.rows), n, what="vector chain"))
             for k, row in enumerate(b.rows):
-                dst = vp(d_streams + 4 * k * stride)
                 if isinstance(row, tuple):
-                    if n:
-                        _engine.check(lib.sdfk_memcpy_d2d(dst, vp(row[0] + 4 * first), n * 4), "d2d")
-                elif n:
-                    _engine.check(lib.sdfk_memcpy_h2d(dst, _engine._ptr(row[first:first + n]), n * 4), "h2d")
+                    streams.copy_from(row[0] + 4 * first, n * 4, streams.offset(k))
+                else:
+                    streams.upload(row[first:first + n], streams.offset(k))
         out_stride = result.stride if out_kind == 0 else stride
-        _engine.check(lib.sdfk_vec_eval_device(prog, len(b.instr), vp(d_p), n, p_stride, vp(d_streams) if d_streams else None,
-                                               len(b.rows), stride, out_kind, vp(result.ptr), out_stride, None),
+        _engine.check(lib.sdfk_vec_eval_device(prog, len(b.instr), vp(p.ptr), n, p.stride,
+                                               streams.at() if streams is not None else None, len(b.rows), stride, out_kind,
+                                               vp(result.ptr), out_stride, None),
                       "sdfk_vec_eval_device")
         _engine.check(lib.sdfk_sync(None), "sdfk_sync")
-    finally:
-        if own_p is not None:
-            own_p.free()
-        if d_streams:
-            lib.sdfk_free(vp(d_streams))
+        on_error.pop_all()
     if out_kind != 0:
         result.n = n                                             # allocated with the padded length: 16-byte row ends
     if resident:
@@ -413,20 +396,17 @@ def _run(b, p_arr, grid_axes, out_kind, config):
     streams = np.stack(b.rows) if b.rows else None
     out = np.empty((3, n) if out_kind == 0 else (n,), dtype=np.float32)
     if grid_axes is not None:
-        ax = [np.ascontiguousarray(a, dtype=np.float32) for a in grid_axes]
+        _, tab = _engine.axis_args(grid_axes)
         host, dtype = None, 0
     else:
-        ax = [None, None, None]
+        tab = (None, 0) * 3
         host = p_arr
         if host.dtype not in (np.float32, np.float64):
             host = host.astype(np.float64)
         host = np.ascontiguousarray(host)
         dtype = 0 if host.dtype == np.float32 else 1
     _engine.check(lib.sdfk_vec_eval_host(
-        prog, len(b.instr), _engine._ptr(host) if host is not None else None, dtype, n,
-        _engine._ptr(ax[0]) if ax[0] is not None else None, ax[0].size if ax[0] is not None else 0,
-        _engine._ptr(ax[1]) if ax[1] is not None else None, ax[1].size if ax[1] is not None else 0,
-        _engine._ptr(ax[2]) if ax[2] is not None else None, ax[2].size if ax[2] is not None else 0,
+        prog, len(b.instr), _engine._ptr(host) if host is not None else None, dtype, n, *tab,
         _engine._ptr(streams) if streams is not None else None, len(b.rows), out_kind, _engine._ptr(out), config.device),
         "sdfk_vec_eval_host")
     if config.output_dtype is not np.float32:

@@ -28,13 +28,14 @@ Reverse mode (vjp, value_and_grad_sse): one pass of the adjoint kernel (csrc/sdf
 a restore tape, back-propagates a cotangent per point and reduces P̄ = Σ_i c_i ∂f_i/∂P on the device in float64; the host
 applies θ̄ = dP/dθ · P̄ with the float64 rows of parameter_tangents (not rounded). Gradients have JAX's grad structure.
 """
+import contextlib
 import ctypes
 import inspect
 
 import numpy as np
 
 from . import _engine, _ops
-from ._eval import config
+from ._eval import config, device_coords
 from ._ir import CombineSDF, ModSDF, NodeSDF, PrimSDF, UnsupportedSDF
 from ._lower import OWNED, Lowerer, NeedsStage, _deep
 
@@ -221,79 +222,24 @@ def parameter_tangents(builder, primals, argnums=0):
 # ---------------------------------------------------------------------------------------------------
 # device plumbing
 # ---------------------------------------------------------------------------------------------------
-def _stride(n):
-    return (n + 63) // 64 * 64
-
-
-class _Coords:
-    """(3, N) coordinates on the device: a DeviceVectorField, a generate_grid array (filled on the device from its axis
-    tables) or a host array (uploaded as fp32, as create() does). aegolius_amd.render uploads its rays through this class
-    too (`ptr`, `stride`, `n`, `free()`)."""
-
-    def __init__(self, co):
-        L = _engine.lib()
-        self.owned = None
-        if isinstance(co, _engine.DeviceVectorField):
-            self.ptr, self.stride, self.n = co.row_ptr(0), co.stride, co.n
-            return
-        axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
-        if axes is not None:
-            ax = [np.ascontiguousarray(a, dtype=np.float32) for a in axes]
-            self.n = int(ax[0].size * ax[1].size * ax[2].size)
-        else:
-            host = np.asarray(co)
-            if host.ndim != 2 or host.shape[0] != 3:
-                raise ValueError("coordinates must have shape (3, N); got %r" % (host.shape,))
-            host = np.ascontiguousarray(host, dtype=np.float32)
-            self.n = int(host.shape[1])
-        self.stride = _stride(self.n)
-        self.owned = self.ptr = L.sdfk_malloc(max(3 * self.stride, 64) * 4)
-        if not self.ptr:
-            raise _engine.SdfkError("autodiff: out of device memory for the coordinates")
-        if axes is not None:
-            _engine.grid_fill(self.ptr, self.stride, ax, 0, self.n)
-        else:
-            for r in range(3):
-                if self.n:
-                    _engine.check(L.sdfk_memcpy_h2d(_engine._vp(self.ptr + 4 * r * self.stride), _engine._ptr(host[r]),
-                                                    self.n * 4), "sdfk_memcpy_h2d")
-
-    def free(self):
-        if self.owned:
-            _engine.lib().sdfk_free(_engine._vp(self.owned))
-            self.owned = None
-
-
 def _run(prog, coords, rows, seed_points=False):
     """rows: (K <= 4, n_params) fp32 parameter tangents -> (value DeviceField, [K tangent DeviceFields])."""
     L = _engine.lib()
     vp = _engine._vp
     n, K = coords.n, rows.shape[0]
     dP = np.ascontiguousarray(rows, dtype=np.float32)
-    d_dp = L.sdfk_malloc(max(dP.size, 1) * 4)
-    tstride = _stride(n)
-    d_t = L.sdfk_malloc(max(K * tstride, 64) * 4)
-    try:
-        if not d_dp or not d_t:
-            raise _engine.SdfkError("autodiff: out of device memory")
-        if dP.size:
-            _engine.check(L.sdfk_memcpy_h2d(vp(d_dp), _engine._ptr(dP), dP.size * 4), "sdfk_memcpy_h2d")
-        value = _engine.DeviceField(n, config.device)
-        _engine.check(L.sdfk_eval_jvp_device(prog.handle, vp(coords.ptr), n, coords.stride, vp(d_dp), K,
-                                             1 if seed_points else 0, vp(value.ptr), vp(d_t), tstride, None),
+    with contextlib.ExitStack() as on_error, _engine.DeviceBuffer(dP.size * 4, what="autodiff") as d_dp, \
+            _engine.DeviceRows(K, n, what="autodiff") as d_t:
+        d_dp.upload(dP)
+        value = on_error.enter_context(_engine.DeviceField(n, config.device))
+        _engine.check(L.sdfk_eval_jvp_device(prog.handle, vp(coords.ptr), n, coords.stride, d_dp.at(), K,
+                                             1 if seed_points else 0, vp(value.ptr), d_t.at(), d_t.stride, None),
                       "sdfk_eval_jvp_device")
-        tangents = []
-        for k in range(K):
-            t = _engine.DeviceField(n, config.device)
-            if n:
-                _engine.check(L.sdfk_memcpy_d2d(vp(t.ptr), vp(d_t + 4 * k * tstride), n * 4), "sdfk_memcpy_d2d")
-            tangents.append(t)
+        tangents = [on_error.enter_context(_engine.DeviceField.from_device(d_t.row_ptr(k), n, config.device))
+                    for k in range(K)]
         _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        on_error.pop_all()
         return value, tangents
-    finally:
-        for d in (d_dp, d_t):
-            if d:
-                L.sdfk_free(vp(d))
 
 
 def _host(field):
@@ -306,8 +252,7 @@ def _evaluate_channels(prog, co, rows, resident):
     """All channels of `rows` (m, n_params), in groups of GROUP per launch -> (value, [m tangents])."""
     _engine.require_gpu()
     _engine.check(_engine.lib().sdfk_set_device(config.device), "sdfk_set_device")
-    coords = _Coords(co)
-    try:
+    with device_coords(co, "autodiff") as coords:
         value, tangents = None, []
         groups = [rows[i:i + GROUP] for i in range(0, rows.shape[0], GROUP)] or [np.zeros((1, rows.shape[1]), np.float32)]
         for block in groups:
@@ -318,8 +263,6 @@ def _evaluate_channels(prog, co, rows, resident):
                 v.free()
             tangents.extend(ts)
         tangents = tangents[:rows.shape[0]]
-    finally:
-        coords.free()
     if resident:
         return value, tangents
     return _host(value), [_host(t) for t in tangents]
@@ -378,11 +321,8 @@ def value_and_grad_points(geometry, co, resident=False):
     prog = _program(low, origin)
     _engine.require_gpu()
     _engine.check(_engine.lib().sdfk_set_device(config.device), "sdfk_set_device")
-    coords = _Coords(co)
-    try:
+    with device_coords(co, "autodiff") as coords:
         value, grads = _run(prog, coords, np.zeros((3, low.params.size), dtype=np.float32), seed_points=True)
-    finally:
-        coords.free()
     if resident:
         return value, grads
     host = [_host(g) for g in grads]
@@ -464,16 +404,13 @@ def _adjoint_program(low, origin):
 
 
 def _point_count(co):
-    """N of what _Coords accepts, on the host (nothing touches the GPU)."""
+    """N of what _eval.device_coords accepts, on the host (nothing touches the GPU)."""
     if isinstance(co, _engine.DeviceVectorField):
         return int(co.n)
     axes = getattr(co, "grid_axes", None) if config.grid_fast_path else None
     if axes is not None:
         return int(np.prod([np.asarray(a).size for a in axes]))
-    shape = np.shape(co)
-    if len(shape) != 2 or shape[0] != 3:
-        raise ValueError("coordinates must have shape (3, N); got %r" % (shape,))
-    return int(shape[1])
+    return _engine.coords_n(np.shape(co))
 
 
 def _check_size(x, n, what):
@@ -497,22 +434,18 @@ def _reverse(prog, co, d_in, mode, generic, n_params):
     L = _engine.lib()
     vp = _engine._vp
     _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
-    coords = _Coords(co)
-    owned = None
-    try:
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        coords = stack.enter_context(device_coords(co, "autodiff"))
         if not isinstance(d_in, _engine.DeviceField):
-            owned = d_in = _engine.DeviceField.from_host(np.asarray(d_in, dtype=np.float32), config.device)
-        value = _engine.DeviceField(coords.n, config.device)
+            d_in = stack.enter_context(_engine.DeviceField.from_host(np.asarray(d_in, dtype=np.float32), config.device))
+        value = on_error.enter_context(_engine.DeviceField(coords.n, config.device))
         pbar = np.zeros(n_params, dtype=np.float64)
         loss = ctypes.c_double(0.0)
         _engine.check(L.sdfk_eval_vjp_device(prog.handle, vp(coords.ptr), coords.n, coords.stride, vp(d_in.ptr), mode,
                                              1 if generic else 0, vp(value.ptr), _engine._ptr(pbar), ctypes.byref(loss),
                                              None), "sdfk_eval_vjp_device")
+        on_error.pop_all()
         return value, pbar, loss.value
-    finally:
-        coords.free()
-        if owned is not None:
-            owned.free()
 
 
 def _grad(builder, co, primals, d_in, argnums, mode, generic, what):

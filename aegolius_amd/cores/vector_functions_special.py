@@ -44,19 +44,10 @@ def compute_crossings_2d(sdf_grid, thr=0.06):
     if a.size == 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
     field, _ = _field(a)
-    lib = _engine.lib()
-    d_sign = lib.sdfk_malloc(a.size)
-    try:
-        if not d_sign:
-            raise _engine.SdfkError("compute_crossings_2d: out of device memory")
-        _engine.check(lib.sdfk_field_crossings_2d(_engine._vp(field.ptr), None, a.shape[0], a.shape[1], 1, 1.0, 1.0,
-                                                  float(thr), _engine._vp(d_sign), None), "sdfk_field_crossings_2d")
-        out = np.empty(a.shape, dtype=np.int8)
-        _engine.check(lib.sdfk_memcpy_d2h(_engine._ptr(out), _engine._vp(d_sign), out.size), "sdfk_memcpy_d2h")
-    finally:
-        if d_sign:
-            lib.sdfk_free(_engine._vp(d_sign))
-        field.free()
+    with field, _engine.DeviceBuffer(a.size, what="compute_crossings_2d") as d_sign:
+        _engine.check(_engine.lib().sdfk_field_crossings_2d(_engine._vp(field.ptr), None, a.shape[0], a.shape[1], 1, 1.0, 1.0,
+                                                            float(thr), d_sign.at(), None), "sdfk_field_crossings_2d")
+        out = d_sign.download(np.empty(a.shape, dtype=np.int8))
     return out.astype(np.int64)
 
 

@@ -453,7 +453,7 @@ def _gpu_gradient(ext, shape):
     lib, vp = _engine.lib(), _engine._vp
     torch.cuda.synchronize()
     n = ext.numel()
-    stride = (n + 63) // 64 * 64
+    stride = _engine.row_stride(n)
     dims = (1,) * (3 - len(shape)) + tuple(shape)
     vec = torch.empty((len(shape), stride), dtype=torch.float32, device=ext.device)
     _engine.check(lib.sdfk_field_gradient(vp(ext.data_ptr()), dims[0], dims[1], dims[2], len(shape), 1,

@@ -21,7 +21,7 @@ Output definition (the kernels and tests/mesh_reference.py implement exactly thi
   * 2-D: the same per square (16 cases); point (i, j) owns its +x and +y edges; each segment (a, b) has the inside on
     its left, so an inside region is bounded counter-clockwise and a hole clockwise.
 """
-import ctypes
+import contextlib
 import struct
 
 import numpy as np
@@ -196,71 +196,16 @@ def _extract(field, tables, level, timings=None):
     if _points(field) != n:
         raise ValueError("the field has %d values; the axes span %s = %d points" % (_points(field), "x".join(map(str, shape)), n))
     lv = _level(level)
-    own = None
-    if isinstance(field, _engine.DeviceField):
-        dev = field
-        dev._live()
-    else:
-        dev = own = _engine.DeviceField.from_host(np.asarray(field, dtype=np.float32).ravel(), _device())
-    L = _engine.lib()
-    c = ctypes
-    nv, nf = _engine._i64(0), _engine._i64(0)
-    bufs = []
-
-    def alloc(nbytes):
-        p = L.sdfk_malloc(max(int(nbytes), 1))
-        if not p:
-            raise _engine.SdfkError("mesh: out of device memory (%d bytes)" % nbytes)
-        bufs.append(p)
-        return c.c_void_p(p)
-
-    ev = []
-
-    def mark():
-        if timings is not None:
-            e = _engine.Event()
-            e.record()
-            ev.append(e)
-
-    try:
-        mark()
-        if dims == 3:
-            d_scratch = alloc(L.sdfk_field_isosurface_scratch(*shape))
-            _engine.check(L.sdfk_field_isosurface(c.c_void_p(dev.ptr), _engine._ptr(tables[0]), shape[0], _engine._ptr(tables[1]),
-                                                  shape[1], _engine._ptr(tables[2]), shape[2], lv, c.byref(nv), c.byref(nf),
-                                                  d_scratch, None), "sdfk_field_isosurface")
+    with contextlib.ExitStack() as stack:
+        if isinstance(field, _engine.DeviceField):
+            dev = field
+            dev._live()
         else:
-            d_scratch = alloc(L.sdfk_field_contour2d_scratch(*shape))
-            _engine.check(L.sdfk_field_contour2d(c.c_void_p(dev.ptr), _engine._ptr(tables[0]), shape[0], _engine._ptr(tables[1]),
-                                                 shape[1], lv, c.byref(nv), c.byref(nf), d_scratch, None), "sdfk_field_contour2d")
-        mark()
-        V, F = nv.value, nf.value
-        wide = V > 0x7fffffff
-        d_v = alloc(V * dims * 4)
-        d_f = alloc(F * dims * (8 if wide else 4))
-        if dims == 3:
-            _engine.check(L.sdfk_field_isosurface_finish(c.c_void_p(dev.ptr), shape[0], shape[1], shape[2], lv, V, F, d_v, V, d_f, F,
-                                                         8 if wide else 4, d_scratch, None), "sdfk_field_isosurface_finish")
-        else:
-            _engine.check(L.sdfk_field_contour2d_finish(c.c_void_p(dev.ptr), shape[0], shape[1], lv, V, F, d_v, V, d_f, F,
-                                                        8 if wide else 4, d_scratch, None), "sdfk_field_contour2d_finish")
-        mark()
-        verts = np.empty((V, dims), dtype=np.float32)
-        faces = np.empty((F, dims), dtype=np.int64 if wide else np.int32)
-        if V:
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(verts), d_v, verts.nbytes), "sdfk_memcpy_d2h")
-        if F:
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(faces), d_f, faces.nbytes), "sdfk_memcpy_d2h")
-        mark()
-        if timings is not None:
-            for name, a, b in zip(("count", "emit", "copy"), ev, ev[1:]):
-                timings[name] = a.elapsed_ms(b)
-        return verts, faces.astype(np.int64, copy=False)
-    finally:
-        for p in bufs:
-            L.sdfk_free(c.c_void_p(p))
-        if own is not None:
-            own.free()
+            dev = stack.enter_context(_engine.DeviceField.from_host(np.asarray(field, dtype=np.float32).ravel(), _device()))
+        _, tab = _engine.axis_args(tables)
+        d_field = (_engine._vp(dev.ptr),)
+        verts, faces = _engine.extract_mesh("sdfk_field", shape, lv, d_field + tab, d_field + shape, timings=timings)
+    return verts, faces.astype(np.int64, copy=False)
 
 
 def _device():

@@ -42,14 +42,15 @@ the kernel the record {eye, fwd, du, dv} in float32 and the kernel generates the
 `Camera.rays` is the same formula on the host in float64. The hit threshold is the pixel's footprint: `cone` defaults
 to tan(fov / 2) / H, half the angular size of a pixel (orthographic: `eps` defaults to height / (2 H), half a pixel).
 """
+import contextlib
 import ctypes
 
 import numpy as np
 
 from . import _engine, _lipschitz, _ops
-from ._eval import config, program_for
+from ._eval import config, device_coords, program_for
 from ._lower import OWNED, NeedsStage, _deep
-from .autodiff import UnsupportedOpError, _Coords, _TracingLowerer      # (autodiff.py marks both as used from here)
+from .autodiff import UnsupportedOpError, _TracingLowerer      # (autodiff.py marks the lowerer as used from here)
 
 MISS, HIT, LIMIT = 0, 1, 2
 STENCIL_FLOOR = np.float32(2.0 ** -16)        # csrc/sdfk_raydev.h sdfk_ray_stencil_width
@@ -314,48 +315,24 @@ class Image:
 
 
 # ---- device plumbing ----------------------------------------------------------------------------------------------------
-class _Outputs:
-    def __init__(self, n, normals):
-        L = _engine.lib()
-        self.n = n
-        self.t = self.normals = self.d_status = self.d_steps = None
-        try:
-            self.t = _engine.DeviceField(n, config.device)
-            self.normals = _engine.DeviceVectorField(n, config.device) if normals else None
-            self.d_status = L.sdfk_malloc(max(n, 64))
-            self.d_steps = L.sdfk_malloc(max(n, 16) * 4)
-            if not self.d_status or not self.d_steps:
-                raise _engine.SdfkError("render: out of device memory")
-        except BaseException:
-            self.free()
-            raise
-
-    def small(self):
-        status = np.empty(self.n, dtype=np.uint8)
-        steps = np.empty(self.n, dtype=np.int32)
-        if self.n:
-            L = _engine.lib()
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(status), _engine._vp(self.d_status), self.n), "sdfk_memcpy_d2h")
-            _engine.check(L.sdfk_memcpy_d2h(_engine._ptr(steps), _engine._vp(self.d_steps), self.n * 4), "sdfk_memcpy_d2h")
-        return status, steps
-
-    def free(self, keep=False):
-        L = _engine.lib()
-        for name in ("d_status", "d_steps"):
-            p = getattr(self, name, None)
-            if p:
-                L.sdfk_free(_engine._vp(p))
-                setattr(self, name, None)
-        if not keep:
-            for field in (self.t, self.normals):
-                if field is not None:
-                    field.free()
+def _outputs(fields, scratch, n, normals):
+    """The trace kernels' outputs, entered on two ExitStacks: t (DeviceField) and the normals (DeviceVectorField or
+    None) on `fields`, the status bytes and int32 steps (DeviceBuffers) on `scratch`."""
+    t = fields.enter_context(_engine.DeviceField(n, config.device))
+    nrm = fields.enter_context(_engine.DeviceVectorField(n, config.device)) if normals else None
+    d_status = scratch.enter_context(_engine.DeviceBuffer(max(n, 64), what="render"))
+    d_steps = scratch.enter_context(_engine.DeviceBuffer(max(n, 16) * 4, what="render"))
+    return t, nrm, d_status, d_steps
 
 
-def _normal_args(out):
-    if out.normals is None:
+def _small(n, d_status, d_steps):
+    return d_status.download(np.empty(n, dtype=np.uint8)), d_steps.download(np.empty(n, dtype=np.int32))
+
+
+def _normal_args(nrm):
+    if nrm is None:
         return None, 0
-    return _engine._vp(out.normals.ptr), out.normals.stride
+    return _engine._vp(nrm.ptr), nrm.stride
 
 
 # ---- public interface ---------------------------------------------------------------------------------------------------
@@ -387,33 +364,20 @@ def cast(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0
     L = _engine.lib()
     _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
     vp = _engine._vp
-    co, cd, out = None, None, None
-    try:
-        co = _Coords(origins)
-        cd = _Coords(directions)
-        out = _Outputs(n_o, normals)
-        d_n, nstride = _normal_args(out)
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        co = stack.enter_context(device_coords(origins, "render"))
+        cd = stack.enter_context(device_coords(directions, "render"))
+        t, nrm, d_status, d_steps = _outputs(on_error, stack, n_o, normals)
+        d_n, nstride = _normal_args(nrm)
         _engine.check(L.sdfk_trace_rays_device(prog.handle, vp(co.ptr), co.stride, vp(cd.ptr), cd.stride, n_o, t_min, t_max,
-                                               eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(out.t.ptr),
-                                               vp(out.d_status), vp(out.d_steps), d_n, nstride, None, config.mode),
-                      "sdfk_trace_rays_device")
+                                               eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(t.ptr), d_status.at(),
+                                               d_steps.at(), d_n, nstride, None, config.mode), "sdfk_trace_rays_device")
         _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = out.small()
+        status, steps = _small(n_o, d_status, d_steps)
         if resident:
-            out.free(keep=True)
-            return RayHits(out.t, status, steps, out.normals, origins, directions)
-        t = out.t.numpy()
-        nrm = out.normals.numpy() if normals else None
-        out.free()
-        return RayHits(t, status, steps, nrm, origins, directions)
-    except BaseException:
-        if out is not None:
-            out.free()
-        raise
-    finally:
-        for c in (co, cd):
-            if c is not None:
-                c.free()
+            on_error.pop_all()
+            return RayHits(t, status, steps, nrm, origins, directions)
+        return RayHits(t.numpy(), status, steps, nrm.numpy() if normals else None, origins, directions)
 
 
 def render(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=256, lipschitz=None, normals=True, eps=None,
@@ -434,19 +398,17 @@ def render(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=25
     vp = _engine._vp
     n = width * height
     rec = camera.record(width, height)
-    out = _Outputs(n, normals)
-    try:
-        d_n, nstride = _normal_args(out)
+    with contextlib.ExitStack() as stack:
+        t, nrm, d_status, d_steps = _outputs(stack, stack, n, normals)
+        d_n, nstride = _normal_args(nrm)
         _engine.check(L.sdfk_trace_camera_device(prog.handle, _engine._ptr(rec), width, height, 1 if camera.ortho else 0, t_min,
-                                                 t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(out.t.ptr),
-                                                 vp(out.d_status), vp(out.d_steps), d_n, nstride, None, config.mode),
+                                                 t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(t.ptr),
+                                                 d_status.at(), d_steps.at(), d_n, nstride, None, config.mode),
                       "sdfk_trace_camera_device")
         _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = out.small()
-        t = out.t.numpy().reshape(height, width)
-        nrm = np.ascontiguousarray(out.normals.numpy().T).reshape(height, width, 3) if normals else None
-    finally:
-        out.free()
+        status, steps = _small(n, d_status, d_steps)
+        t = t.numpy().reshape(height, width)
+        nrm = np.ascontiguousarray(nrm.numpy().T).reshape(height, width, 3) if normals else None
     status = status.reshape(height, width)
     depth = np.where(status == HIT, t, np.float32(np.inf)).astype(np.float32)
     return Image(depth, status, steps.reshape(height, width), nrm, t=t, camera=camera, eps=float(eps), cone=float(cone))

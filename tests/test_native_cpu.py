@@ -27,6 +27,28 @@ def test_library_exports_every_declared_symbol(built):
     assert built.device_count() >= 0
 
 
+def test_device_memory_has_one_owner_and_one_layout():
+    """Device memory is allocated and freed by _engine.DeviceBuffer alone, the row stride of staged arrays and the check
+    of (3, N) coordinates are each written once: a new front end builds on them instead of bringing its own."""
+    pkg = os.path.join(ROOT, "aegolius_amd")
+    sources = {}
+    for folder in (pkg, os.path.join(pkg, "cores")):
+        for name in sorted(os.listdir(folder)):
+            if name.endswith(".py"):
+                sources[os.path.relpath(os.path.join(folder, name), pkg)] = open(os.path.join(folder, name)).read()
+
+    def lines(needle):
+        return [(f, ln.strip()) for f, text in sources.items() for ln in text.splitlines() if needle in ln]
+    engine = sources["_engine.py"]
+    buffer_class = engine[engine.index("class DeviceBuffer"):engine.index("class DeviceRows")]
+    for needle in ("sdfk_malloc", "sdfk_free"):
+        hits = lines(needle)
+        assert {f for f, _ in hits} == {"_engine.py"}, hits
+        assert len(hits) == 2 and sum(needle in ln for ln in buffer_class.splitlines()) == 1, hits    # SIGNATURES + the class
+    assert len(lines("+ 63) // 64")) == 1, lines("+ 63) // 64")
+    assert len(lines("coordinates must have shape (3, N)")) == 1, lines("coordinates must have shape (3, N)")
+
+
 def test_opcode_table_is_consistent(built):
     assert len(_ops.OPS) == len(set(o.name for o in _ops.OPS)) >= 80
     hdr = open(os.path.join(ROOT, "aegolius_amd", "csrc", "sdfk_device.h")).read()

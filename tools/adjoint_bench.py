@@ -35,7 +35,7 @@ def main():
     __graft_entry__.build()
     import aegolius_amd.cores as ns
     from aegolius_amd.cores.helper_functions import grid_axes
-    from aegolius_amd import _engine, autodiff as ad, workloads
+    from aegolius_amd import _engine, _eval, autodiff as ad, workloads
 
     _engine.require_gpu()
     L = _engine.lib()
@@ -89,7 +89,7 @@ def main():
             grid_axes = axes
         n = int(np.prod([a.size for a in axes]))
         run = {"size": size, "points": n, "n_params": ns_, "tape_floats_per_point": None}
-        coords = ad._Coords(co)
+        coords = _eval.device_coords(co)
         d_c = _engine.DeviceField.from_host(np.ones(n, dtype=np.float32))
         d_v = L.sdfk_malloc(n * 4)
         d_t = L.sdfk_malloc(4 * coords.stride * 4)

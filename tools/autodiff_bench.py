@@ -86,7 +86,7 @@ def main():
         field = _engine.DeviceField(n)
         run["create_ms"], run["create_all"] = timed(lambda: prog.eval_grid(axes, 0, n, field.ptr), args.reps)
         field.free()
-        coords = ad._Coords(co)
+        coords = _eval.device_coords(co)
         stride = coords.stride
         d_v = L.sdfk_malloc(n * 4)
         d_t = L.sdfk_malloc(4 * stride * 4)

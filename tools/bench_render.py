@@ -7,6 +7,7 @@ around the launch alone (outputs pre-allocated, kernel already built), rays/s, p
 MODE_NOCULL) on a (3, M) array of M = that many random points — and the ratio of the two rates; the wave efficiency of the
 8 x 8 tile mapping against a row-major one, from the steps image. Prints one JSON line."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -85,10 +86,10 @@ def main():
     eps, cone = cam.footprint(W, H)
     rec = cam.record(W, H)
     inv = float(np.float32(1.0 / low.lipschitz))
-    out = render._Outputs(n, True)
     result = {"scene": args.scene, "width": W, "height": H, "instructions": int(low.code.shape[0]), "lipschitz": low.lipschitz,
               "chain_members": prog.chain_members, "device": "MI355X (gfx950), 1 GPU", "kernels": {}}
-    try:
+    with contextlib.ExitStack() as stack:
+        t, normals, d_status, d_steps = render._outputs(stack, stack, n, True)
         for name in args.modes.split(","):
             ray_mode = {"interpret": _engine.MODE_INTERPRET, "specialised": _engine.MODE_SPECIALIZED}[name]
             field_mode = {"interpret": _engine.MODE_INTERPRET, "specialised": _engine.MODE_NOCULL}[name]
@@ -99,10 +100,10 @@ def main():
             def launch():
                 _engine.check(L.sdfk_trace_camera_device(prog.handle, _engine._ptr(rec), W, H, 0, 0.0, float(np.float32(args.t_max)),
                                                          float(np.float32(eps)), float(np.float32(cone)), inv, args.max_steps,
-                                                         vp(out.t.ptr), vp(out.d_status), vp(out.d_steps), vp(out.normals.ptr),
-                                                         out.normals.stride, None, ray_mode), "sdfk_trace_camera_device")
+                                                         vp(t.ptr), d_status.at(), d_steps.at(), vp(normals.ptr),
+                                                         normals.stride, None, ray_mode), "sdfk_trace_camera_device")
             k["ms"], k["ms_min"] = median_ms(launch, args.reps, args.warmup)
-            status, steps = out.small()
+            status, steps = render._small(n, d_status, d_steps)
             evals = int(steps.sum()) + n + 4 * int(np.count_nonzero(status == render.HIT))
             k.update(rays_per_s=n / (k["ms"] * 1e-3), evaluations=evals, evaluations_per_s=evals / (k["ms"] * 1e-3),
                      hits=int(np.count_nonzero(status == render.HIT)), step_limit=int(np.count_nonzero(status == render.LIMIT)),
@@ -122,8 +123,6 @@ def main():
             k["field_points_per_s"] = evals / (k["field_ms"] * 1e-3)
             k["ratio_to_field_kernel"] = k["evaluations_per_s"] / k["field_points_per_s"]
             result["kernels"][name] = k
-    finally:
-        out.free()
     print(json.dumps(result))
 
 
