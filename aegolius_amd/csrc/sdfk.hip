@@ -221,7 +221,7 @@ struct SpecModule {                   // a code object loaded on one device
     std::mutex mu;
     bool loaded = false, failed = false;
     hipModule_t mod = nullptr;
-    hipFunction_t fn[2] = {nullptr, nullptr};
+    hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // ([2], [3]: the culled pair of the ray flavour)
     std::string error;
 };
 
@@ -1333,6 +1333,14 @@ static std::shared_ptr<SpecModule> get_module(sdfk_program* p, int device, int f
             const bool grid_fl = flavour == SDFK_FL_ROWS_GRID || flavour == SDFK_FL_ROWS2D_GRID;
             if (hipModuleGetFunction(&m->fn[1], m->mod, grid_fl ? "sdfk_spec_cellsg" : "sdfk_spec_cells") != hipSuccess) {
                 m->fn[1] = nullptr;
+                (void)hipGetLastError();
+            }
+        }
+        if (he == hipSuccess && flavour == SDFK_FL_RAYS) {
+            // long chains come with a second pair of kernels that cull along the rays (sdfk_codegen.cpp: kRaysCull)
+            if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_rays_cull") != hipSuccess ||
+                hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_raycam_cull") != hipSuccess) {
+                m->fn[2] = m->fn[3] = nullptr;
                 (void)hipGetLastError();
             }
         }

@@ -13,6 +13,13 @@
 //     otherwise: step limit
 // One ray per lane. The loop runs while any lane of the wave still marches: the trip count is wave-uniform, so the
 // evaluator's code words stay scalar loads; lanes that have finished evaluate along and are masked out of every update.
+//
+// The wave-level hook. Before every evaluation the loop calls field.prepare(p, t, active, reach) in wave-uniform control
+// flow: `active` marks the lanes whose value will be used (the marching lanes; at the normal, the lanes that hit), and
+// the evaluations that follow stay within `reach` of this lane's p (0 along the ray; the stencil's reach at the normal).
+// A field may bound the active points of the wave and cull its members for them (the specialised chain-mode kernels:
+// sdfk_codegen.cpp, SdfkCullField); the interpreter's field ignores the call. The hook returns nothing and the value of
+// an active lane must not depend on it: the marching arithmetic below is the same with and without.
 #ifndef SDFK_RAYDEV_H
 #define SDFK_RAYDEV_H
 
@@ -91,7 +98,8 @@ static __device__ __forceinline__ float sdfk_ray_stencil_width(float thr, V3 p) 
     return fmaxf(thr, 1.52587890625e-05f * m);
 }
 
-// FIELD: float operator()(V3) const — the program at one point (interpreter switch or the generated sdfk_point<float>)
+// FIELD: float operator()(V3) const — the program at one point (interpreter switch or the generated sdfk_point<float>);
+//        void prepare(V3 p, float t, bool active, float reach) const — the wave-level hook (see the head of this file)
 template <typename SRC, typename FIELD>
 static __device__ __forceinline__ void sdfk_trace(const SRC& src, const FIELD& field, const sdfk_rayopts R,
                                                   float* __restrict__ out_t, unsigned char* __restrict__ out_status,
@@ -107,6 +115,7 @@ static __device__ __forceinline__ void sdfk_trace(const SRC& src, const FIELD& f
     for (int it = 0; it < R.max_steps; ++it) {
         if (!__any(marching)) break;
         const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
+        field.prepare(p, t, marching, 0.0f);
         const float f = field(p);
         if (marching) {
             thr = fmaxf(R.eps, R.cone * t);
@@ -136,6 +145,9 @@ static __device__ __forceinline__ void sdfk_trace(const SRC& src, const FIELD& f
     if (__any(hit)) {
         const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
         const float h = sdfk_ray_stencil_width(thr, p);
+        // the four stencil points lie within sqrt(3) h of p, plus the rounding of p + h k: at most 2^-24 max|p| <= 2^-8 h
+        // per component by the floor of h — 1.75 > sqrt(3) (1 + 2^-8)
+        field.prepare(p, t, hit, 1.75f * h);
         V3 g = {0.0f, 0.0f, 0.0f};
         _Pragma("unroll 1") for (int k = 0; k < 4; ++k) {       // (one call site: the body is inlined once, not four times)
             const float kx = (k == 0 || k == 3) ? 1.0f : -1.0f, ky = (k >= 2) ? 1.0f : -1.0f,

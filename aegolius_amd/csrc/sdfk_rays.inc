@@ -8,7 +8,9 @@
 //     one-point-per-lane instantiations (compiler's resource remarks, all four instances: 57 VGPRs, 8 waves per SIMD):
 //     the small coordinate file stays in VGPRs and its three value registers, indexed by the wave-uniform operand
 //     fields, take 16 bytes of scratch per lane (sdfk_interp_kernel<1, 2, 3>: 16 as well); the full file takes 128.
-//   * the specialised flavour (SDFK_FL_RAYS, sdfk_codegen.cpp) wraps the generated sdfk_point<float> in the same loop.
+//   * the specialised flavour (SDFK_FL_RAYS, sdfk_codegen.cpp) wraps the generated sdfk_point<float> in the same loop;
+//     long hard unions (chain mode) get a second pair of kernels there that folds the chain over per-wave survivor
+//     lists in LDS (kRaysCull) — what SPECIALIZED / AUTO launch, NOCULL the plain pair; same bits.
 // Outputs per ray: t (fp32), status (1 byte: 0 miss, 1 hit, 2 step limit), steps (int32), optionally the stencil normal
 // (three strided rows). Plain vector stores, written once; no atomics, no LDS.
 #include "sdfk_raydev.h"
@@ -20,6 +22,7 @@ struct SdfkInterpField {
     const float* __restrict__ prm;
     const float* __restrict__ tab;
     int result_reg;
+    __device__ __forceinline__ void prepare(V3, float, bool, float) const {}   // (the wave-level hook: nothing to cull here)
     __device__ __forceinline__ float operator()(V3 p0) const {
         constexpr bool SPLIT = NC <= SDFK_NC_SMALL;             // (see sdfk_interp_kernel)
         float CX[SPLIT ? NC : 1], CY[SPLIT ? NC : 1], CZ[SPLIT ? NC : 1];
@@ -111,6 +114,40 @@ static int rays_options(const char* who, float t_min, float t_max, float eps, fl
     return 0;
 }
 
+// test aid: what the culled ray kernels of a -DSDFK_DEBUG_RAYSTATS=1 build counted (sdfk_debug_rays_stats). One buffer of
+// 8 counters per process; a launch that counts is synchronised and read back at once.
+static std::atomic<bool> g_rays_stats_on{false};
+static std::mutex g_rays_stats_mu;
+static long long g_rays_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+extern "C" void sdfk_debug_rays_stats(int enable, long long* out8) {
+    g_rays_stats_on.store(enable != 0);
+    if (out8) {
+        std::lock_guard<std::mutex> lk(g_rays_stats_mu);
+        for (int i = 0; i < 8; ++i) out8[i] = g_rays_stats[i];
+        for (int i = 0; i < 8; ++i) g_rays_stats[i] = 0;
+    }
+}
+static int rays_stats_buffer(unsigned long long** out, hipStream_t stream) {
+    unsigned long long* b = nullptr;
+    HIPCHK(hipMalloc(&b, 8 * sizeof(unsigned long long)));
+    if (hipMemsetAsync(b, 0, 8 * sizeof(unsigned long long), stream) != hipSuccess) {   // (ordered with the launch that counts)
+        (void)hipFree(b);
+        return fail(-2, "sdfk_debug_rays_stats: hipMemsetAsync failed");
+    }
+    *out = b;
+    return 0;
+}
+static int rays_stats_collect(unsigned long long* b, hipStream_t stream) {
+    unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = hipMemcpy(h, b, sizeof h, hipMemcpyDeviceToHost);
+    (void)hipFree(b);
+    if (e != hipSuccess) return fail(-2, std::string("sdfk_debug_rays_stats: ") + hipGetErrorString(e));
+    std::lock_guard<std::mutex> lk(g_rays_stats_mu);
+    for (int i = 0; i < 8; ++i) g_rays_stats[i] += (long long)h[i];
+    return 0;
+}
+
 // array rays (cam == nullptr) or camera rays; `count` = rays (array) or pixels (camera)
 static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, const sdfk_camera* cam, long long count,
                     const sdfk_rayopts& opts, float* d_t, unsigned char* d_status, int* d_steps, float* d_normals,
@@ -153,14 +190,25 @@ static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, 
     const float* tab = d->d_tables;
     sdfk_rayopts o = opts;
     if (sk) {
-        if (cam) {
-            sdfk_camera c = *cam;
-            void* args[] = {&prm, &tab, &c, &o, &d_t, &d_status, &d_steps, &d_normals, &nstride};
-            HIPCHK(hipModuleLaunchKernel(sk->fn[1], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args, nullptr));
-        } else {
-            SdfkRaysArray a = *arr;
-            void* args[] = {&prm, &tab, &a, &o, &d_t, &d_status, &d_steps, &d_normals, &nstride};
-            HIPCHK(hipModuleLaunchKernel(sk->fn[0], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args, nullptr));
+        // the culled pair (long chains only) unless the caller asked for the kernel without culling; one more argument,
+        // the counters of the statistics build (null otherwise)
+        const bool cull = mode != SDFK_MODE_NOCULL && sk->fn[2] && sk->fn[3];
+        unsigned long long* stats = nullptr;
+        if (cull && g_rays_stats_on.load()) {
+            rc = rays_stats_buffer(&stats, stream);
+            if (rc) return rc;
+        }
+        sdfk_camera c;
+        SdfkRaysArray a;
+        void* src = cam ? (void*)&c : (void*)&a;
+        if (cam) c = *cam;
+        else a = *arr;
+        void* args[] = {&prm, &tab, src, &o, &d_t, &d_status, &d_steps, &d_normals, &nstride, &stats};
+        HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (cam ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
+                                     nullptr));
+        if (stats) {
+            rc = rays_stats_collect(stats, stream);
+            if (rc) return rc;
         }
         return 0;
     }

@@ -41,6 +41,15 @@ vectors fwd = (target - eye) / |target - eye|, right = fwd x up / |fwd x up|, up
 the kernel the record {eye, fwd, du, dv} in float32 and the kernel generates the rays itself — no ray array exists;
 `Camera.rays` is the same formula on the host in float64. The hit threshold is the pixel's footprint: `cone` defaults
 to tan(fov / 2) / H, half the angular size of a pixel (orthographic: `eps` defaults to height / (2 H), half a pixel).
+
+Long hard unions and intersections (from 64 members on, among the trees the field kernels run "in chain mode") are culled along
+the rays. The 64 rays of a wave — an 8 x 8 pixel tile in `render`, 64 consecutive rays in `cast` — bound the points they
+are about to evaluate by a sphere, every member is evaluated once at its centre, and only the members that can be the
+minimum (maximum) somewhere in that sphere are folded per ray, in their original order; waves whose rays have drifted apart
+split into up to 8 groups by t, and what still does not fit runs every member. The members left out are larger than the
+minimum at every point of the sphere, so the result has the bits of the kernel without culling (`config.mode =
+MODE_NOCULL` runs that one; tests/test_gpu_render_cull.py compares the two), whatever the order of the rays. Coherent rays
+are what makes it fast: a 1000-sphere union costs a few dozen member evaluations per step instead of 1000.
 """
 import contextlib
 import ctypes

@@ -40,7 +40,8 @@ extern "C" {
                                    straight-line program; same FP semantics, same bits) */
 #define SDFK_MODE_INTERPRET 1   /* generic register-machine interpreter kernel */
 #define SDFK_MODE_SPECIALIZED 2 /* wait for the specialised kernel; fail instead of falling back if hiprtc fails */
-#define SDFK_MODE_NOCULL 3      /* specialised kernel with brick culling switched off (A/B runs, tests) */
+#define SDFK_MODE_NOCULL 3      /* specialised kernel with brick culling switched off (A/B runs, tests); along rays: the
+                                   plain ray kernel, without the per-wave survivor lists of long unions */
 
 typedef struct sdfk_program sdfk_program;
 
@@ -115,6 +116,15 @@ int sdfk_program_compile_flavour(sdfk_program* prog, int flavour, size_t* code_s
  * fine cells without a list (their bricks probe every member), empty cells }; out8 (nullable) receives the record of the
  * last such launch and clears it. */
 void sdfk_debug_cells_stats(int enable, long long* out8);
+/* Test aid: with enable != 0 every launch of a culled ray kernel that was built with -DSDFK_DEBUG_RAYSTATS=1
+ * (sdfk_debug_set_rtc_defs) is synchronised and its counters are added to a record; out8 (nullable) receives the record
+ * and clears it: { list builds, member evaluations of those builds, survivor evaluations, plain-loop evaluations,
+ * splits, point evaluations, 0, 0 }. Survivor and plain-loop evaluations are in lane slots — 64 per wave and evaluation,
+ * whatever the number of marching lanes, as the hardware spends them: a list of n survivors adds 64 n to the third, a
+ * group that ran every member 64 to the fourth; a point evaluation is one evaluation call of one wave. So
+ * (builds' evaluations + survivor evaluations + members * plain-loop evaluations) / 64 per point evaluation is the number
+ * of members a lane paid for per evaluation; in the plain kernel that is every member. */
+void sdfk_debug_rays_stats(int enable, long long* out8);
 /* Test aid: build one flavour the way BACKGROUND builds are run — in a child process (aegolius_amd/sdfk_rtc_helper,
  * csrc/sdfk_rtc_helper.c) — and return the code-object size; nothing is cached. While the interpreter kernel serves the
  * first calls of a new tree shape (SDFK_MODE_AUTO) the compiler never runs inside the calling process: hiprtc holds a
@@ -505,8 +515,10 @@ int sdfk_eval_grid_contour2d_finish(sdfk_program* prog, const float* ax0, int64_
  * the hit as three rows of normal_stride floats: the four-point tetrahedron difference of the field with the
  * half-width h = max(thr, 2^-16 * max(|x|, |y|, |z|)) of the hit point, the zero vector for rays that did not hit.
  * Directions must be unit vectors (not checked on the device). Asynchronous on `stream`. `mode` selects the kernel as
- * for sdfk_eval_device (SDFK_MODE_NOCULL = SDFK_MODE_SPECIALIZED here: rays are never culled): the interpreter
- * kernel and the specialised one (SDFK_FLAVOUR_RAYS) give the same bits; programs beyond the interpreter's register
+ * for sdfk_eval_device: the interpreter kernel and the specialised ones (SDFK_FLAVOUR_RAYS) give the same bits. A long
+ * hard union (chain mode) is traced by a kernel that culls its members per wave — a survivor list in LDS for the
+ * sphere around the points the wave evaluates next — under SDFK_MODE_SPECIALIZED and SDFK_MODE_AUTO, and by the plain
+ * kernel, every member at every step, under SDFK_MODE_NOCULL; for every other program the two are the same kernel; programs beyond the interpreter's register
  * file run on the specialised kernel only. Arguments are validated on the host — t_max < t_min, max_steps <= 0, a
  * non-finite or non-positive inv_lipschitz, negative eps / cone return -1 and launch nothing. */
 /* 0: the program can be traced; 1: it reads an auxiliary field (V_FIELD: staged evaluation, defined on a grid only),
