@@ -59,6 +59,7 @@ SIGNATURES = {
     "sdfk_field_min": (_int, [_vp, _i64, _c.POINTER(_c.c_float), _vp]),
     "sdfk_grid_box_average": (_int, [_vp, _i64, _i64, _i64, _int, _int, _int, _int, _vp, _vp]),
     "sdfk_grid_edge_detect": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "sdfk_debug_box_variant": (_int, [_i64, _i64, _i64, _int, _int, _int, _c.POINTER(_int)]),
     "sdfk_grid_signed": (_int, [_vp, _i64, _i64, _i64, _c.c_float, _int, _vp, _vp]),
     "sdfk_grid_boundary_mask": (_int, [_vp, _i64, _c.c_float, _vp, _vp]),
     "sdfk_grid_signed_slab": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp]),

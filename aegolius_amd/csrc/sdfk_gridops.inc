@@ -191,16 +191,62 @@ __global__ __launch_bounds__(256) void sdfk_box_march_kernel(const float* __rest
     }
 }
 
+// Which kernel a box launch takes, decided in ONE place: the launch below and sdfk_debug_box_variant (the tests' view of
+// the dispatch) both read it, so the query cannot drift from the launch.
+struct BoxVariant {
+    bool march, fast, flat;
+    int k0c, k2c;              // template arguments (k0c: marching kernel only; k2c 0 = run-time k2)
+    int pc, chunks;            // tiled: halo planes per LDS chunk and ceil(k0 / pc); marching: planes per segment, 1
+    GridDims d;                // the grid and the kernel as the device kernels see them: a flat field (n2 == 1) is
+    int k0, k1, k2;            //   relabelled (1, n0, n1) and its kernel (1, k0, k1); k2 is folded away
+    dim3 grid;
+    size_t lds;
+};
+static int box_variant(GridDims d, int k0, int k1, int k2, BoxVariant* v) {
+    v->flat = d.n2 == 1;
+    if (v->flat) {                                            // flat field: threads along its contiguous axis
+        d = GridDims{1, d.n0, d.n1};
+        k2 = k1; k1 = k0; k0 = 1;
+    }
+    v->d = d;
+    v->k0 = k0; v->k1 = k1; v->k2 = k2;
+    v->fast = k0 / 2 <= d.n0 && k1 / 2 <= d.n1 && k2 / 2 <= d.n2;       // taps reach at most one field width outside
+    const int hjm = SDFK_BOXM_TJ + k1 - 1, hk = SDFK_BOX_TK + k2 - 1;
+    const unsigned kt = (unsigned)((d.n2 + SDFK_BOX_TK - 1) / SDFK_BOX_TK);
+    v->march = v->fast && k0 <= 7 && k0 != 6 && (long long)hjm * hk <= 1024    // 4 halo cells per thread; reflections one field deep
+               && (d.n1 + SDFK_BOXM_TJ - 1) / SDFK_BOXM_TJ <= 65535 && (d.n0 + SDFK_BOXM_SEG - 1) / SDFK_BOXM_SEG <= 65535
+               && !getenv("SDFK_BOX_NO_MARCH");                          // A/B switch for the bench tool
+    if (v->march) {
+        int seg = SDFK_BOXM_SEG;
+        if (const char* e = getenv("SDFK_BOXM_SEG")) seg = std::max(1, atoi(e));             // experiments
+        v->k0c = k0;
+        v->k2c = (k2 == 1 || k2 == 3 || k2 == 5) ? k2 : 0;
+        v->pc = seg;
+        v->chunks = 1;
+        v->grid = dim3(kt, (unsigned)((d.n1 + SDFK_BOXM_TJ - 1) / SDFK_BOXM_TJ), (unsigned)((d.n0 + seg - 1) / seg));
+        v->lds = (size_t)2 * hjm * hk * sizeof(double);
+        return 0;
+    }
+    const long long plane = (long long)(SDFK_BOX_TJ + k1 - 1) * hk;
+    if (plane > 7500) return fail(-1, "grid operator: kernel too wide for the LDS tile ((k1 + 3) * (k2 + 63) <= 7500)");
+    v->pc = (int)std::max<long long>(1, std::min<long long>(k0, 7500 / plane));              // planes per LDS chunk
+    v->chunks = (k0 + v->pc - 1) / v->pc;
+    v->lds = (size_t)v->pc * plane * sizeof(double);
+    const unsigned gy = (unsigned)((d.n1 + SDFK_BOX_TJ - 1) / SDFK_BOX_TJ);
+    if (d.n0 > 65535 || gy > 65535) return fail(-1, "grid operator: grid dimension beyond the launch limits");
+    // workgroups in flight: enough to fill the chip several times over, few enough that each walks several k-tiles
+    const long long rows = (long long)gy * d.n0;
+    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(kt, (16384 + rows - 1) / rows));
+    v->grid = dim3(gx, gy, (unsigned)d.n0);
+    v->k0c = 0;
+    v->k2c = !v->fast ? 0 : (k2 <= 5 || k2 == 7) ? k2 : 0;
+    return 0;
+}
+
 template <int K0C>
-static void box_march_go(const float* src, float* dst, GridDims d, int k1, int k2, double inv, int edge, hipStream_t stream) {
-    const int hj = SDFK_BOXM_TJ + k1 - 1, hk = SDFK_BOX_TK + k2 - 1;
-    const size_t lds = (size_t)2 * hj * hk * sizeof(double);
-    int seg = SDFK_BOXM_SEG;
-    if (const char* e = getenv("SDFK_BOXM_SEG")) seg = std::max(1, atoi(e));                 // experiments
-    const dim3 grid((unsigned)((d.n2 + SDFK_BOX_TK - 1) / SDFK_BOX_TK), (unsigned)((d.n1 + SDFK_BOXM_TJ - 1) / SDFK_BOXM_TJ),
-                    (unsigned)((d.n0 + seg - 1) / seg));
-#define SDFK_BOXM_GO(K2) hipLaunchKernelGGL((sdfk_box_march_kernel<K0C, K2>), grid, dim3(256), lds, stream, src, dst, d, k1, k2, inv, edge, seg)
-    switch (k2) {
+static void box_march_go(const float* src, float* dst, const BoxVariant& v, double inv, int edge, hipStream_t stream) {
+#define SDFK_BOXM_GO(K2) hipLaunchKernelGGL((sdfk_box_march_kernel<K0C, K2>), v.grid, dim3(256), v.lds, stream, src, dst, v.d, v.k1, v.k2, inv, edge, v.pc)
+    switch (v.k2c) {
         case 1: SDFK_BOXM_GO(1); break;
         case 3: SDFK_BOXM_GO(3); break;
         case 5: SDFK_BOXM_GO(5); break;
@@ -208,41 +254,22 @@ static void box_march_go(const float* src, float* dst, GridDims d, int k1, int k
     }
 #undef SDFK_BOXM_GO
 }
-// true if the marching kernel took the launch
-static bool box_march_launch(const float* src, float* dst, GridDims d, int k0, int k1, int k2, double inv, int edge, hipStream_t stream) {
-    const int hj = SDFK_BOXM_TJ + k1 - 1, hk = SDFK_BOX_TK + k2 - 1;
-    const bool fast = k0 / 2 <= d.n0 && k1 / 2 <= d.n1 && k2 / 2 <= d.n2;
-    if (!fast || k0 > 7 || k0 == 6 || hj * hk > 1024) return false;      // 4 halo cells per thread; reflections one field deep
-    if ((d.n1 + SDFK_BOXM_TJ - 1) / SDFK_BOXM_TJ > 65535 || (d.n0 + SDFK_BOXM_SEG - 1) / SDFK_BOXM_SEG > 65535) return false;
-    if (getenv("SDFK_BOX_NO_MARCH")) return false;                        // A/B switch for the bench tool
-    switch (k0) {
-        case 1: box_march_go<1>(src, dst, d, k1, k2, inv, edge, stream); break;
-        case 2: box_march_go<2>(src, dst, d, k1, k2, inv, edge, stream); break;
-        case 3: box_march_go<3>(src, dst, d, k1, k2, inv, edge, stream); break;
-        case 4: box_march_go<4>(src, dst, d, k1, k2, inv, edge, stream); break;
-        case 5: box_march_go<5>(src, dst, d, k1, k2, inv, edge, stream); break;
-        default: box_march_go<7>(src, dst, d, k1, k2, inv, edge, stream); break;
-    }
-    return true;
-}
 
-static int box_launch(const float* src, float* dst, GridDims d, int k0, int k1, int k2, double inv, int edge, hipStream_t stream) {
-    if (box_march_launch(src, dst, d, k0, k1, k2, inv, edge, stream)) return 0;
-    const long long plane = (long long)(SDFK_BOX_TJ + k1 - 1) * (SDFK_BOX_TK + k2 - 1);
-    if (plane > 7500) return fail(-1, "grid operator: kernel too wide for the LDS tile ((k1 + 3) * (k2 + 63) <= 7500)");
-    const int pc = (int)std::max<long long>(1, std::min<long long>(k0, 7500 / plane));      // planes per LDS chunk
-    const size_t lds = (size_t)pc * plane * sizeof(double);
-    const unsigned gy = (unsigned)((d.n1 + SDFK_BOX_TJ - 1) / SDFK_BOX_TJ);
-    if (d.n0 > 65535 || gy > 65535) return fail(-1, "grid operator: grid dimension beyond the launch limits");
-    // workgroups in flight: enough to fill the chip several times over, few enough that each walks several k-tiles
-    const unsigned kt = (unsigned)((d.n2 + SDFK_BOX_TK - 1) / SDFK_BOX_TK);
-    const long long rows = (long long)gy * d.n0;
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(kt, (16384 + rows - 1) / rows));
-    const dim3 grid(gx, gy, (unsigned)d.n0);
-    const bool fast = k0 / 2 <= d.n0 && k1 / 2 <= d.n1 && k2 / 2 <= d.n2;   // taps reach at most one field width outside
-#define SDFK_BOX_GO(F, K) hipLaunchKernelGGL((sdfk_box_kernel<F, K>), grid, dim3(256), lds, stream, src, dst, d, k0, k1, k2, inv, edge, pc)
-    if (!fast) SDFK_BOX_GO(false, 0);
-    else switch (k2) {
+static void box_launch(const float* src, float* dst, const BoxVariant& v, double inv, int edge, hipStream_t stream) {
+    if (v.march) {
+        switch (v.k0c) {
+            case 1: box_march_go<1>(src, dst, v, inv, edge, stream); break;
+            case 2: box_march_go<2>(src, dst, v, inv, edge, stream); break;
+            case 3: box_march_go<3>(src, dst, v, inv, edge, stream); break;
+            case 4: box_march_go<4>(src, dst, v, inv, edge, stream); break;
+            case 5: box_march_go<5>(src, dst, v, inv, edge, stream); break;
+            default: box_march_go<7>(src, dst, v, inv, edge, stream); break;
+        }
+        return;
+    }
+#define SDFK_BOX_GO(F, K) hipLaunchKernelGGL((sdfk_box_kernel<F, K>), v.grid, dim3(256), v.lds, stream, src, dst, v.d, v.k0, v.k1, v.k2, inv, edge, v.pc)
+    if (!v.fast) SDFK_BOX_GO(false, 0);
+    else switch (v.k2c) {
         case 1: SDFK_BOX_GO(true, 1); break;
         case 2: SDFK_BOX_GO(true, 2); break;
         case 3: SDFK_BOX_GO(true, 3); break;
@@ -252,7 +279,6 @@ static int box_launch(const float* src, float* dst, GridDims d, int k0, int k1, 
         default: SDFK_BOX_GO(true, 0); break;
     }
 #undef SDFK_BOX_GO
-    return 0;
 }
 
 // ---- signed ------------------------------------------------------------------------------------------------
@@ -524,18 +550,16 @@ extern "C" int sdfk_grid_box_average(float* d_field, int64_t n0, int64_t n1, int
     if (iterations == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = (long long)n0 * n1 * n2;
-    if (d.n2 == 1) {                                          // flat field: threads along its contiguous axis
-        d = GridDims{1, d.n0, d.n1};
-        k2 = k1; k1 = k0; k0 = 1;
-    }
+    BoxVariant v;
+    rc = box_variant(d, k0, k1, k2, &v);
+    if (rc) return rc;
     Scratch sc;
     if (sc.get(d_scratch, (size_t)n * sizeof(float))) return fail(-5, "sdfk_grid_box_average: out of device memory");
     float* d_tmp = static_cast<float*>(sc.p);
-    const double inv = 1.0 / ((double)k0 * k1 * k2);
+    const double inv = 1.0 / ((double)v.k0 * v.k1 * v.k2);
     float *src = d_field, *dst = d_tmp;
     for (int it = 0; it < iterations; ++it) {
-        rc = box_launch(src, dst, d, k0, k1, k2, inv, 0, stream);
-        if (rc) return rc;
+        box_launch(src, dst, v, inv, 0, stream);
         std::swap(src, dst);
     }
     hipError_t e = hipGetLastError();
@@ -553,20 +577,33 @@ extern "C" int sdfk_grid_edge_detect(float* d_field, int64_t n0, int64_t n1, int
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const long long n = (long long)n0 * n1 * n2;
-    int flat = 0;
-    if (d.n2 == 1) {
-        d = GridDims{1, d.n0, d.n1};
-        flat = 1;
-    }
+    BoxVariant v;
+    rc = box_variant(d, 3, 3, 1, &v);                          // (a flat field: (1, 3, 3) on (1, n0, n1))
+    if (rc) return rc;
     Scratch sc;
     if (sc.get(d_scratch, (size_t)n * sizeof(float))) return fail(-5, "sdfk_grid_edge_detect: out of device memory");
     float* d_tmp = static_cast<float*>(sc.p);
-    rc = flat ? box_launch(d_field, d_tmp, d, 1, 3, 3, 1.0, 1, stream) : box_launch(d_field, d_tmp, d, 3, 3, 1, 1.0, 1, stream);
-    if (rc) return rc;
+    box_launch(d_field, d_tmp, v, 1.0, 1, stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(d_field, d_tmp, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail(-6, std::string("sdfk_grid_edge_detect: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// Test aid (host only, launches nothing): the variant box_launch would run for this grid and kernel.
+extern "C" int sdfk_debug_box_variant(int64_t n0, int64_t n1, int64_t n2, int k0, int k1, int k2, int* out8) {
+    GridDims d;
+    if (!out8) return fail(-1, "sdfk_debug_box_variant: null output");
+    int rc = grid_dims_ok(n0, n1, n2, &d, "sdfk_debug_box_variant");
+    if (rc) return rc;
+    if (k0 < 1 || k1 < 1 || k2 < 1) return fail(-1, "sdfk_debug_box_variant: bad kernel size");
+    BoxVariant v;
+    rc = box_variant(d, k0, k1, k2, &v);
+    if (rc) return rc;
+    const int out[8] = {(v.march ? 1 : 0) | (v.fast ? 2 : 0) | (v.flat ? 4 : 0), v.k0c, v.k2c, v.pc, v.chunks,
+                        (int)v.grid.x, (int)v.grid.y, (int)v.grid.z};
+    memcpy(out8, out, sizeof out);
     return 0;
 }
 

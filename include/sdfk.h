@@ -255,6 +255,12 @@ int sdfk_grid_box_average(float* d_field, int64_t n0, int64_t n1, int64_t n2, in
 int sdfk_grid_edge_detect(float* d_field, int64_t n0, int64_t n1, int64_t n2, void* d_scratch, void* stream);
 int sdfk_grid_signed(float* d_field, int64_t n0, int64_t n1, int64_t n2, float sep_min, int crop, void* d_scratch,
                      void* stream);
+/* Test aid (host only, launches nothing): which box kernel sdfk_grid_box_average would run for this grid and kernel
+ * (sdfk_grid_edge_detect: k = 3, 3, 1). The launch reads the same decision. out8 = { flags: 1 = marching kernel
+ * (else the tiled one), 2 = FAST reflection (kernel at most twice the field), 4 = flat field relabelled (1, n0, n1);
+ * K0C (marching kernel, else 0); K2C (0 = run-time k2); marching: planes per segment, tiled: halo planes per LDS chunk;
+ * LDS chunks per output (marching: 1); the launch grid x, y, z }. Honours SDFK_BOX_NO_MARCH and SDFK_BOXM_SEG. */
+int sdfk_debug_box_variant(int64_t n0, int64_t n1, int64_t n2, int k0, int k1, int k2, int* out8);
 /* `signed` on ONE SLAB of a grid that is sharded over several GPUs: the scan lines cross every slab, but all they
  * read is one bit per point (field < sep_min). sdfk_grid_boundary_mask writes that test for n points as bytes; the
  * ranks exchange the bytes (aegolius_amd/distributed.py); sdfk_grid_signed_slab runs the scans on the WHOLE grid's
