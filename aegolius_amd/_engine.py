@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libsdfk.so")
 
 MODE_AUTO, MODE_INTERPRET, MODE_SPECIALIZED, MODE_NOCULL = 0, 1, 2, 3
 (FLAVOUR_PLAIN_ARRAY, FLAVOUR_PLAIN_GRID, FLAVOUR_TILE_ARRAY, FLAVOUR_TILE_GRID, FLAVOUR_TILE_MASK, FLAVOUR_ROWS_ARRAY,
- FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID, FLAVOUR_RAYS) = range(11)
+ FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID, FLAVOUR_RAYS, FLAVOUR_OCCUPANCY) = range(12)
 FLAVOUR_FLAGS = 0x100      # OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (fused selection)
 FLAVOUR_XY = 0x200         # OR-ed onto PLAIN_ARRAY / ROWS2D_ARRAY: the build for two-row coordinates (z = 0 by contract)
 
@@ -136,6 +136,10 @@ SIGNATURES = {
                                       _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
     "sdfk_trace_camera_device": (_int, [_vp, _vp, _int, _int, _int, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                         _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
+    "sdfk_eval_grid_occupancy_scratch": (_sz, [_i64, _i64, _i64, _i64]),
+    "sdfk_eval_grid_occupancy": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float,
+                                        _c.c_float, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64), _fp, _vp, _int]),
+    "sdfk_field_row_sums": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
 }
 
 
@@ -509,6 +513,40 @@ class Program:
         lead = (self._h,) + tab
         return extract_mesh("sdfk_eval_grid", [a.size for a in ax], level, lead, lead, (mode,), timings)
 
+    def occupancy_grid(self, axes, sub_tables, half_widths, samples, level, lipschitz, d_out, slab_cells=0, device=0,
+                       mode=MODE_AUTO, timings=None):
+        """Occupancy fractions of the cells of the grid the three axis tables span (sdfk_eval_grid_occupancy), written to
+        the device pointer `d_out` (one float per cell): count / K of the K sub-samples the three `sub_tables` span per
+        cell; `half_widths`: per axis and grid point, a float32 bound of the distance to its farthest sub-sample.
+        `lipschitz`: the bound the skip rule uses (inf: nothing is skipped). aegolius_amd.occupancy builds the tables and
+        states the definition. -> (inside sub-samples, near cells) as Python ints. `timings`: a dict that receives
+        device-event milliseconds of centre / classify / sample."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(axes)
+        if len(ax) != 3 or len(sub_tables) != 3 or len(half_widths) != 3:
+            raise ValueError("occupancy_grid: three axis, sub-sample and half-width tables")
+        k = [int(samples) if a.size > 1 else 1 for a in ax]
+        sub = [np.ascontiguousarray(t, dtype=np.float32) for t in sub_tables]
+        hw = [np.ascontiguousarray(t, dtype=np.float32) for t in half_widths]
+        for a, s, h, ka in zip(ax, sub, hw, k):
+            if s.shape != (a.size * ka,) or h.shape != (a.size,):
+                raise ValueError("occupancy_grid: an axis of %d points takes %d sub-samples and %d half-widths; got %r and %r"
+                                 % (a.size, a.size * ka, a.size, s.shape, h.shape))
+        shape = [a.size for a in ax]
+        inside, near = _i64(0), _i64(0)
+        ms = (_c.c_float * 3)() if timings is not None else None
+        with DeviceBuffer(L.sdfk_eval_grid_occupancy_scratch(*shape, int(slab_cells)), what="occupancy") as scratch:
+            check(L.sdfk_eval_grid_occupancy(self._h, *tab, *[_ptr(s) for s in sub], *[_ptr(h) for h in hw], int(samples),
+                                             float(level), float(lipschitz), _vp(d_out), scratch.at(), int(slab_cells),
+                                             ctypes.byref(inside), ctypes.byref(near), ms, None, mode),
+                  "sdfk_eval_grid_occupancy")
+        if timings is not None:
+            for name, value in zip(("centre", "classify", "sample"), ms):
+                timings[name] = timings.get(name, 0.0) + float(value)
+        return int(inside.value), int(near.value)
+
     def select_host(self, co, threshold=0.0, device=0, mode=MODE_AUTO):
         """The same for a (3, N) host array (uploaded once as float32; the row-length hint is detected like create())."""
         require_gpu()
@@ -696,6 +734,18 @@ class DeviceField(DeviceBuffer):
         check(lib().sdfk_field_gradient(_vp(self.ptr), shape[0], shape[1], shape[2], 3, 1 if normalize else 0, _vp(out.ptr),
                                         out.stride, None), "sdfk_field_gradient")
         return out
+
+
+def field_row_sums(d_field, rows, row_len, weights):
+    """sum_i field[r, i] * weights[i] in float64 for the `rows` rows of `row_len` floats at the device pointer (int)
+    `d_field`, reduced on the device in a fixed order (sdfk_field_row_sums) -> (rows,) float64 host array."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (int(row_len),):
+        raise ValueError("field_row_sums: one weight per point of a row")
+    out = np.empty(int(rows), dtype=np.float64)
+    with DeviceBuffer(max(out.nbytes, 8), what="row sums") as sums:
+        check(lib().sdfk_field_row_sums(_vp(d_field), int(rows), int(row_len), _ptr(w), sums.at(), None), "sdfk_field_row_sums")
+        return sums.download(out)
 
 
 class DeviceVectorField(DeviceRows):

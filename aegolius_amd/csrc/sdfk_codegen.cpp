@@ -91,13 +91,14 @@ extern "C" __global__ __launch_bounds__(SDFK_BLOCK) void sdfk_spec_g1(
 
 // Sphere tracing (SDFK_FL_RAYS): the marching loop of sdfk_raydev.h around the generated body. Array rays and camera rays
 // in one translation unit; the same text as the interpreter ray kernel (sdfk_rays.inc) but for the evaluator.
-static const char kRays[] = R"SDFKW(
+static const char kSpecField[] = R"SDFKW(
 struct SdfkSpecField {
     const float* __restrict__ PRM;
     const float* __restrict__ TAB;
     __device__ __forceinline__ void prepare(V3, float, bool, float) const {}
     __device__ __forceinline__ float operator()(V3 p) const { return sdfk_point<float>(p, PRM, TAB, nullptr, 0); }
-};
+};)SDFKW";
+static const char kRays[] = R"SDFKW(
 extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_rays(
     const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkRaysArray src, sdfk_rayopts opts,
     float* __restrict__ out_t, unsigned char* __restrict__ out_status, int* __restrict__ out_steps,
@@ -112,6 +113,24 @@ extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_raycam(
     const SdfkSpecField field = {PRM, TAB};
     const SdfkRaysCamera src = {cam};
     sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride);
+}
+)SDFKW";
+
+// Sub-voxel occupancy (SDFK_FL_OCCUPANCY): the sample pass of sdfk_occdev.h around the same field object as the plain ray
+// kernels, over a list of cells or over all cells of a slab; the same text as the interpreter sample kernel
+// (sdfk_occupancy.inc) but for the evaluator.
+static const char kOccupancy[] = R"SDFKW(
+extern "C" __global__ __launch_bounds__(SDFK_OCC_BLOCK) void sdfk_spec_occ_list(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkOccList src, sdfk_occgrid grid,
+    float* __restrict__ out) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_occ_sample(src, field, grid, out);
+}
+extern "C" __global__ __launch_bounds__(SDFK_OCC_BLOCK) void sdfk_spec_occ_all(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkOccAll src, sdfk_occgrid grid,
+    float* __restrict__ out) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_occ_sample(src, field, grid, out);
 }
 )SDFKW";
 
@@ -2745,7 +2764,7 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
     g.s += "\n";
     g.s += kEmbeddedAccess;
     char buf[64];
-    if (flavour == SDFK_FL_RAYS) {
+    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY) {
         // Sphere tracing: the plain body, one ray per lane (scalar T: lanes diverge per ray, and two rays per lane would
         // double every wave's tail), inside the marching loop of sdfk_raydev.h. A long hard union that the field kernels
         // run table-driven ("chain mode") keeps its table-driven plain body, which builds in a second whatever the number
@@ -2766,7 +2785,16 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
             snprintf(buf, sizeof buf, "    return V_%d;\n}\n", result_reg);
             g.s += buf;
         }
+        if (flavour == SDFK_FL_OCCUPANCY) {
+            // the sample pass of the occupancy fractions: the same plain body (straight-line, or table-driven for a chain)
+            // in the same field object, inside sdfk_occ_sample; never the culled one
+            g.s += kEmbeddedOccdev;
+            g.s += kSpecField;
+            g.s += kOccupancy;
+            return g.s;
+        }
         g.s += kEmbeddedRaydev;
+        g.s += kSpecField;
         g.s += kRays;
         if (chain) {
             g.s += "\n#ifndef SDFK_RAYS_CULL_MIN_LEAVES\n#define SDFK_RAYS_CULL_MIN_LEAVES 64    // (measured: DESIGN 4.14 has the table)\n#endif\n"

@@ -42,6 +42,7 @@ enum sdfk_flavour {
     SDFK_FL_ROWS2D_ARRAY,      // sdfk_spec_r  built for flat grids (rows along y, z = 0: SDFK_FLAT)
     SDFK_FL_ROWS2D_GRID,       // sdfk_spec_rg built for flat grids
     SDFK_FL_RAYS,              // sdfk_spec_rays + sdfk_spec_raycam: sphere tracing around sdfk_point<float> (sdfk_raydev.h)
+    SDFK_FL_OCCUPANCY,         // sdfk_spec_occ_list + sdfk_spec_occ_all: the sample pass of sdfk_occdev.h around sdfk_point<float>
     SDFK_FL_COUNT,
     SDFK_FL_ALL = SDFK_FL_COUNT   // every evaluation flavour in one unit (sdfk_program_source, developer tools)
 };

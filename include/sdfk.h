@@ -103,6 +103,9 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
 #define SDFK_FLAVOUR_RAYS 10       /* sdfk_spec_rays / sdfk_spec_raycam: sphere tracing (sdfk_trace_rays_device /
                                       sdfk_trace_camera_device) around the straight-line body, one ray per lane; needs no
                                       cull sites and has no FLAGS / XY build. Not part of sdfk_program_compile_check. */
+#define SDFK_FLAVOUR_OCCUPANCY 11  /* sdfk_spec_occ_list / sdfk_spec_occ_all: the sample pass of sdfk_eval_grid_occupancy around
+                                      the same body, one sub-sample per lane; as RAYS: no cull sites needed, no FLAGS / XY
+                                      build, not part of sdfk_program_compile_check. */
 /* OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (one bit per point, value <= threshold, instead of
    the field — what sdfk_eval_device_select / sdfk_eval_grid_select launch). A translation unit of its own: the field
    kernels carry none of it (as a run-time branch it cost the 20-primitive tree 10 % at 1025^3). */
@@ -545,6 +548,34 @@ int sdfk_trace_camera_device(sdfk_program* prog, const float* camera, int width,
                              float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_t,
                              unsigned char* d_status, int* d_steps, float* d_normals, int64_t normal_stride, void* stream,
                              int mode);
+
+/* ---- sub-voxel occupancy (aegolius_amd.occupancy; csrc/sdfk_occupancy.inc, csrc/sdfk_occdev.h) ---------------------
+ * Per cell of the grid of the axis tables (flat index (i0 n1 + i1) n2 + i2), the fraction of its K = k0 k1 k2 sub-sample
+ * points (sub0[i0 k0 + j0], sub1[i1 k1 + j1], sub2[i2 k2 + j2]) whose field value is <= level (NaN: outside); k_a =
+ * samples (1, 2, 4 or 8) on an axis of more than one point and 1 on an axis of one point. d_fraction: n0 n1 n2 floats,
+ * count / K, exact. All tables are HOST pointers: ax* the grid points (n_a floats, what sdfk_eval_grid takes), sub* the
+ * sub-sample coordinates (n_a k_a floats), hw* per grid point an upper bound of its distance to its farthest sub-sample
+ * along that axis (n_a floats). `lipschitz`: |f(p) - f(q)| <= L |p - q|. A cell with
+ *     |f(c) - level| > 1.0001 L rho + L cmag + 1e-6 (1 + |f(c)| + |level|),   rho = sqrt(hw0^2 + hw1^2 + hw2^2),
+ *     cmag = 1e-6 (|cx| + |cy| + |cz| + rho)
+ * (fp32; false if a side is NaN) is entirely in or out and gets 1.0 / 0.0 by its centre value, which the grid kernels of
+ * sdfk_eval_grid compute; only the other cells ("near") are sampled. L = +infinity, or SDFK_MODE_NOCULL: no cell is
+ * skipped and the centre values are not computed. Too small an L gives wrong fractions. The grid is processed in slabs of
+ * whole rows of at most slab_cells cells (<= 0 or more than 2^30: 2^30); d_scratch: *_scratch bytes (8 per slab cell, 8
+ * per 1024 slab cells and 32 KB), 256-byte aligned. *inside_samples = the sum of the counts (integers added on the
+ * device and the host: exact, whatever the order), *near_cells = the cells that were sampled. pass_ms (nullable): 3 floats that receive device-event milliseconds
+ * of the centre values, the classification and the sampling. `mode` as for sdfk_trace_rays_device: the interpreter sample
+ * kernel and the specialised one (SDFK_FLAVOUR_OCCUPANCY) give the same bits. Programs with auxiliary fields are refused
+ * (sdfk_program_rays_check). Synchronous: the stream is idle on return. */
+size_t sdfk_eval_grid_occupancy_scratch(int64_t n0, int64_t n1, int64_t n2, int64_t slab_cells);
+int sdfk_eval_grid_occupancy(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                             int64_t n2, const float* sub0, const float* sub1, const float* sub2, const float* hw0,
+                             const float* hw1, const float* hw2, int samples, float level, float lipschitz, float* d_fraction,
+                             void* d_scratch, int64_t slab_cells, int64_t* inside_samples, int64_t* near_cells, float* pass_ms,
+                             void* stream, int mode);
+/* d_out[r] = sum over i of d_field[r row_len + i] * weights[i] in float64, in a fixed order (weights: HOST, row_len
+ * doubles; d_out: rows doubles, DEVICE). What the volume of the fractions is reduced with. Synchronous. */
+int sdfk_field_row_sums(const float* d_field, int64_t rows, int64_t row_len, const double* weights, double* d_out, void* stream);
 
 #ifdef __cplusplus
 }
