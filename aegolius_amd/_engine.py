@@ -140,6 +140,9 @@ SIGNATURES = {
     "sdfk_eval_grid_occupancy": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float,
                                         _c.c_float, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64), _fp, _vp, _int]),
     "sdfk_field_row_sums": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "sdfk_field_redistance_scratch": (_sz, [_i64, _i64, _i64]),
+    "sdfk_field_redistance": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _int, _vp, _vp,
+                                     _c.POINTER(_i64), _fp, _vp]),
 }
 
 

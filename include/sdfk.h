@@ -577,6 +577,24 @@ int sdfk_eval_grid_occupancy(sdfk_program* prog, const float* ax0, int64_t n0, c
  * doubles; d_out: rows doubles, DEVICE). What the volume of the fractions is reduced with. Synchronous. */
 int sdfk_field_row_sums(const float* d_field, int64_t rows, int64_t row_len, const double* weights, double* d_out, void* stream);
 
+/* ---- redistancing (aegolius_amd.redistance; csrc/sdfk_redistance.inc) ------------------------------------------------
+ * d_out[p] = the signed Euclidean distance of grid point p (flat index (i0 n1 + i1) n2 + i2) to the level set of the
+ * field, the level set being the crossing vertices of sdfk_field_isosurface / sdfk_field_contour2d: negative where
+ * f <= level, NaN counting as outside. The definition, float32 operation by operation, is the module text of
+ * aegolius_amd/redistance.py; the result is the brute-force minimum over all seeds of that expression, bit for bit. ax*:
+ * HOST tables, finite and strictly increasing, n0 and n1 >= 2; n2 = 1 is a 2-D grid (ax2 is then not read). band <= 0:
+ * none; else finite, the distance is cut at it: min(D, band). near: 0 = the distance to the seeds alone, 1 = the points
+ * at the ends of crossing edges take min(D, |f - level| / |grad f|) in addition. d_field (n0 n1 n2 floats) is only
+ * read and must not be d_out. d_scratch: *_scratch bytes = 2 n0 n1 n2 floats, nothing is written beyond them. *seeds =
+ * the number of seeds (crossing edges). pass_ms (nullable): SDFK_REDISTANCE_PASSES floats that receive device-event
+ * milliseconds, 3-D: the passes x, xy, y, yx (merged), z of the merged, z, zx, zxy, then the finish; 2-D: x, xy, y, yx,
+ * finish, the rest 0. Synchronous: the stream is idle on return. */
+#define SDFK_REDISTANCE_PASSES 9
+size_t sdfk_field_redistance_scratch(int64_t n0, int64_t n1, int64_t n2);
+int sdfk_field_redistance(const float* d_field, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                          int64_t n2, float level, float band, int near, float* d_out, void* d_scratch, int64_t* seeds,
+                          float* pass_ms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
