@@ -556,10 +556,13 @@ SDFK_DUAL_V_C(dual_prim_cone) {
     const float t2 = sd_clip01(u2);
     const float bx = sd_fma(-q0, t2, w0), by = w1 - q1;
     const float da2 = sd_fma(ax, ax, ay * ay), db2 = sd_fma(bx, bx, by * by);
-    const float d = sd_min(da2, db2);
+    // Which of the side (a) and the base (b) the tangent follows is decided by the clips where they decide it, not by
+    // the two squared distances, which tie in fp32 beside the rim's two normals (see dual_prim_triangle2): both contain
+    // the rim, so one that is clipped to the rim is never the nearer of the two.
+    const bool ta = (u2 >= 1.0f) ? true : ((u1 >= 1.0f) ? false : da2 <= db2);
     const float s = sd_max(-sd_fma(w0, q1, -w1 * q0), -(w1 - q1));
     const float sg = sd_sign(s);
-    const float half_inv = 0.5f * sdd_rcp(sd_sqrt(d));
+    const float half_inv = 0.5f * sdd_rcp(sd_sqrt(ta ? da2 : db2));
     float dw0[K], dw1[K], du1[K], du2[K], dt1[K], dt2[K], dA[K], dB[K], dd[K];
     sdd_len2<K>(c.x, c.y, c.dx, c.dy, w0, dw0);
     SDFK_KLOOP {
@@ -576,7 +579,7 @@ SDFK_DUAL_V_C(dual_prim_cone) {
         dA[k] = 2.0f * (ax * dax + ay * day);
         dB[k] = 2.0f * (bx * dbx + by * dby);
     }
-    sdd_min<K>(da2, db2, dA, dB, dd);
+    SDFK_KLOOP dd[k] = ta ? dA[k] : dB[k];
     SDFK_KLOOP r.d[k] = sg * dd[k] * half_inv;
     return r;
 }
@@ -633,7 +636,18 @@ SDFK_DUAL_V_C(dual_prim_rbox2) {
 SDFK_DUAL_V_C(dual_prim_triangle2) {
     DS<K> r;
     r.v = prim_triangle2(dc_p(c), P, T);
-    float dmin = 3.0e38f, cmin = 3.0e38f;
+    // The tangent follows the nearest edge among those that the clips leave standing, and is the derivative of that
+    // edge's own distance. Squared distances alone do not decide it: beside the normal erected at a vertex, the edge with
+    // a free foot and its neighbour clipped to that vertex differ by the square of the angle to the normal, which fp32
+    // does not resolve (and the offset v - e of an edge clipped to its end cancels), while their gradients differ by the
+    // angle itself. Consecutive edges share a vertex, so an edge clipped to its end (t >= 1) is never nearer than the
+    // next edge, and one clipped to its start (t <= 0) never nearer than the previous edge unless that one is clipped to
+    // its end: such edges are left out. What stands is a free foot, or the offset c - p_i from the vertex itself.
+    float tt[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        tt[i] = sd_dot2(c.x - P[2 * i], c.y - P[2 * i + 1], P[6 + 2 * i], P[7 + 2 * i]) * P[12 + i];
+    float dsel = 3.0e38f, kmin = 3.0e38f, cmin = 3.0e38f;
     float ddmin[K];
     SDFK_KLOOP ddmin[k] = 0.0f;
 #pragma unroll
@@ -652,17 +666,20 @@ SDFK_DUAL_V_C(dual_prim_triangle2) {
             dt[k] = ddot * P[12 + i] + dot * SDFK_DQ(k, 12 + i);
         }
         sdd_clip01<K>(t, dt, dh);
-        const bool keep = dmin <= dd;
+        const bool out = t >= 1.0f || (t <= 0.0f && tt[(i + 2) % 3] < 1.0f);
+        const float key = out ? 3.0e38f : dd;
+        const bool keep = kmin <= key;
         SDFK_KLOOP {
             const float dvx = c.dx[k] - SDFK_DQ(k, 2 * i), dvy = c.dy[k] - SDFK_DQ(k, 2 * i + 1);
             const float dqx = dvx - SDFK_DQ(k, 6 + 2 * i) * h - ex * dh[k], dqy = dvy - SDFK_DQ(k, 7 + 2 * i) * h - ey * dh[k];
             const float ddd = 2.0f * (qx * dqx + qy * dqy);
             ddmin[k] = keep ? ddmin[k] : ddd;
         }
-        dmin = sd_min(dmin, dd);
+        dsel = keep ? dsel : dd;
+        kmin = sd_min(kmin, key);
         cmin = sd_min(cmin, P[15] * sd_fma(vx, ey, -vy * ex));
     }
-    const float f = -sd_sign(cmin) * 0.5f * sdd_rcp(sd_sqrt(dmin));
+    const float f = -sd_sign(cmin) * 0.5f * sdd_rcp(sd_sqrt(dsel));
     SDFK_KLOOP r.d[k] = f * ddmin[k];
     return r;
 }

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import aegolius_amd.cores as ns
+import autodiff_liveness
 import autodiff_scenes
 import scenes
 from aegolius_amd import _ops, autodiff as ad
@@ -181,6 +182,162 @@ def test_every_dual_rule_is_exercised(built):
         ad._program(low, origin)
         seen |= {_ops.OPS[int(w) & 255].name for w in low.code[:, 0]}
     assert set(ad.dual_opcodes()) - seen == set()
+
+
+# ---- reach instead of presence: which terms of the rules the scenes checked against the oracle can see -----------------
+_OP_LOWERINGS = {}
+
+
+def _op_lowerings(name):
+    """(geometry, liveness in point mode on the default lowering, liveness in parameter mode over (tx, ty, ang, s) on the
+    shortcut-free lowering) of one OP_GEOMETRIES entry, computed once."""
+    if name not in _OP_LOWERINGS:
+        make = autodiff_scenes.OP_GEOMETRIES[name][0]
+        geo = make(ns, *autodiff_scenes.OP_DEFAULTS)
+        low, origin = ad._lower(geo, shortcuts=True)
+        ad._program(low, origin)
+        free, origin, rows, _c, _l = ad.parameter_tangents(lambda *p: make(ns, *p), autodiff_scenes.OP_DEFAULTS, (0, 1, 2, 3))
+        ad._program(free, origin)
+        _OP_LOWERINGS[name] = (geo, autodiff_liveness.liveness(low, point_mode=True), autodiff_liveness.liveness(free, rows))
+    return _OP_LOWERINGS[name]
+
+
+def _emitted(geometries, shortcuts):
+    seen = set()
+    for geo in geometries:
+        low, _origin = ad._lower(geo, shortcuts=shortcuts)
+        seen |= {_ops.OPS[int(w) & 255].name for w in low.code[:, 0]}
+    return seen
+
+
+# ops that one of the two lowerings cannot emit: the copy of a frozen register and the folded sign of a positive map exist
+# only with the shortcuts on
+DEFAULT_LOWERING_ONLY = {"MOVC", "VEXPFLAG"}
+SHORTCUT_FREE_ONLY = set()
+
+
+def test_every_dual_rule_has_live_input_tangents(built):
+    """Every rule's input-tangent terms are reached: for each opcode of the table some OP_GEOMETRIES entry that lists it
+    as a target feeds it a register whose tangent can be non-zero, in point mode (default lowering) and in parameter mode
+    (shortcut-free lowering, the placement as primals). An opcode that one lowering never emits is exempt there."""
+    point, param = set(), set()
+    for name, (_make, _dim, targets, _regions) in autodiff_scenes.OP_GEOMETRIES.items():
+        _geo, in_point, in_param = _op_lowerings(name)
+        assert set(targets) <= set(ad.dual_opcodes()), name
+        point |= {l.name for l in in_point if l.input} & set(targets)
+        param |= {l.name for l in in_param if l.input} & set(targets)
+    ops = set(ad.dual_opcodes())
+    assert ops - point - SHORTCUT_FREE_ONLY == set()
+    assert ops - param - DEFAULT_LOWERING_ONLY == set()
+    # the exemptions are what they claim: the other lowering never emits them, in any geometry of these tests
+    geos = [_op_lowerings(name)[0] for name in autodiff_scenes.OP_GEOMETRIES]
+    geos += [fn(ns)(*primals) for fn, primals, _a in autodiff_scenes.SCENES.values()]
+    geos += [fn(ns) for fn in autodiff_scenes.POINT_SCENES.values()]
+    assert _emitted(geos, shortcuts=False) & DEFAULT_LOWERING_ONLY == set()
+    assert _emitted(geos, shortcuts=True) & SHORTCUT_FREE_ONLY == set()
+
+
+# parameterised ops whose parameters no scene of SCENES can move, with the reason
+NO_PARAMETER_TANGENT = {
+    "VEXPFLAG": "only the default lowering emits it; parameter mode differentiates the shortcut-free lowering, where the "
+                "pair stays a positive map followed by VSIGN / VHARDBIN (and the rule's tangent is zero by design)",
+}
+
+
+def test_every_parameterised_dual_rule_has_live_parameter_tangents(built):
+    """Every rule's parameter-tangent terms are reached: each opcode with parameters has, in some scene of SCENES, a
+    non-zero tangent row on its own parameter slice."""
+    live = set()
+    for fn, primals, argnums in autodiff_scenes.SCENES.values():
+        low, _origin, rows, _c, _l = ad.parameter_tangents(fn(ns), primals, argnums)
+        live |= {l.name for l in autodiff_liveness.liveness(low, rows) if l.param}
+    want = {o for o in ad.dual_opcodes() if _ops.BY_NAME[o].nparams > 0}
+    assert set(NO_PARAMETER_TANGENT) <= want and not set(NO_PARAMETER_TANGENT) & live
+    assert want - live - set(NO_PARAMETER_TANGENT) == set()
+
+
+def _label_rows(regions, local):
+    """-> [(labels (n,), names)] for each independent branch point of a regions predicate."""
+    lab = np.atleast_2d(regions(local))
+    names = regions.labels if isinstance(regions.labels[0], tuple) else (regions.labels,)
+    assert lab.shape == (len(names), local.shape[1])
+    return list(zip(lab, names))
+
+
+def test_op_geometry_points_reach_every_branch(built):
+    """On the points the GPU tests use, every branch of every branching rule holds at least 3 % of the points (a
+    condition on the inputs: the constants and the placement of the entries are chosen for it)."""
+    from test_gpu_autodiff import _points
+    checked = 0
+    for name, (_make, dim, _targets, regions) in sorted(autodiff_scenes.OP_GEOMETRIES.items()):
+        if regions is None:
+            continue
+        local = autodiff_scenes.local_coordinates(_op_lowerings(name)[0], _points(seed=15, dim=dim))
+        for labels, names in _label_rows(regions, local):
+            assert labels.min() >= 0 and labels.max() < len(names), name
+            share = np.bincount(labels, minlength=len(names)) / labels.size
+            assert np.all(share >= 0.03), "%s: %s" % (name, dict(zip(names, share.round(4))))
+            checked += 1
+    assert checked >= 40
+
+
+def test_regions_follow_the_local_coordinates_of_the_lowering(built):
+    """local_coordinates is the map the placement's XFORM applies: the labels are taken where the rules branch."""
+    from test_gpu_autodiff import _points
+    for name in ("box", "triangle"):
+        geo, _p, _f = _op_lowerings(name)
+        low, _origin = ad._lower(geo, shortcuts=True)
+        assert _ops.OPS[int(low.code[0, 0]) & 255].name == "XFORM"
+        P = low.params64[int(low.code[0, 1]):][:12]
+        co = _points(seed=15, dim=autodiff_scenes.OP_GEOMETRIES[name][1])
+        np.testing.assert_allclose(autodiff_scenes.local_coordinates(geo, co), P[:9].reshape(3, 3).dot(co) - P[9:, None],
+                                   rtol=0, atol=1e-12)
+
+
+def test_frame_predicates_follow_the_lowering(built):
+    """The predicates that re-apply an earlier modification use the frame the lowering uses. The default lowering folds
+    the frame of mirror / linear_instancing into the placement's XFORM, whose x row is then _frame_x of the local
+    coordinates; rotational_symmetry's ROT2D turns by the angle / 2 - phase of _rotsym_regions."""
+    from test_gpu_autodiff import _points
+    co = _points(seed=15)
+
+    def program(name):
+        geo = _op_lowerings(name)[0]
+        low, _origin = ad._lower(geo, shortcuts=True)
+        names = [_ops.OPS[int(w) & 255].name for w in low.code[:, 0]]
+        return geo, low, names
+
+    for name, follower, frame in (("mirror_sphere", "FOLDX", autodiff_scenes._MIRROR),
+                                  ("lininst_sphere", "LININST", autodiff_scenes._LININST[1:])):
+        geo, low, names = program(name)
+        assert names[:2] == ["XFORM", follower], names
+        P = low.params64[int(low.code[0, 1]):][:12]
+        np.testing.assert_allclose(P[:3].dot(co) - P[9],
+                                   autodiff_scenes._frame_x(autodiff_scenes.local_coordinates(geo, co), *frame),
+                                   rtol=0, atol=1e-12, err_msg=name)
+    geo, low, names = program("rotsym_rod")
+    assert names[:3] == ["XFORM", "ROT2D", "ROTSYM"], names
+    P = low.params64[int(low.code[0, 1]):][:12]
+    np.testing.assert_allclose(P[:9].reshape(3, 3).dot(co) - P[9:, None], autodiff_scenes.local_coordinates(geo, co),
+                               rtol=0, atol=1e-12)
+    h = 2 * np.pi / 3 / 2 - 0.5
+    np.testing.assert_allclose(low.params64[int(low.code[1, 1]):][:2], (np.cos(h), np.sin(h)), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(low.params64[int(low.code[2, 1]):][:1], (2 * np.pi / 3,), rtol=0, atol=1e-12)
+
+
+def test_oracle_kink_filter_keeps_the_op_geometries(built):
+    """The float64 oracle alone: the kink filter of the GPU comparison keeps at least 90 % of the points of every entry,
+    along x, y, z and along the four placement primals."""
+    from test_gpu_autodiff import _points, _reference, _spatial_reference
+    for name, (make, dim, _targets, _regions) in sorted(autodiff_scenes.OP_GEOMETRIES.items()):
+        geo = _op_lowerings(name)[0]
+        co = _points(seed=15, dim=dim)
+        for ax in range(3):
+            _D, keep = _spatial_reference(geo, co, ax)
+            assert keep.mean() >= 0.90, "%s axis %d: %.3f kept" % (name, ax, keep.mean())
+        for a in range(4):
+            _D, keep = _reference(lambda *p: make(ns, *p), autodiff_scenes.OP_DEFAULTS, a, None, co)
+            assert keep.mean() >= 0.90, "%s argnum %d: %.3f kept" % (name, a, keep.mean())
 
 
 def test_design_lists_the_dual_rule_table(built):

@@ -104,6 +104,45 @@ def test_parameter_adjoints_of_default_programs(name, engine):
         _close(pbar, want, scale, "%s generic=%s" % (name, generic))
 
 
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.OP_GEOMETRIES))
+def test_vjp_of_every_op_placement(name, engine):
+    """Reverse mode over the placement (tx, ty, ang, s) of one geometry per rule: the adjoint's input-coordinate products
+    of every rule are consumed by XFORM's parameters, and agree with forward mode (which test_gpu_autodiff anchors to the
+    oracle) on both paths."""
+    make, dim, _targets, _regions = autodiff_scenes.OP_GEOMETRIES[name]
+
+    def builder(tx, ty, ang, s):
+        return make(ns, tx, ty, ang, s)
+    primals, argnums = autodiff_scenes.OP_DEFAULTS, (0, 1, 2, 3)
+    co = _points(seed=15, dim=dim)
+    c = np.random.default_rng(17).normal(size=co.shape[1]).astype(np.float32)
+    want, scale, value = _contraction(builder, co, primals, argnums, c)
+    scale = np.maximum(scale, 1e-2 * _parameter_scale(builder, co, primals, argnums, c))
+    v, g = ad.vjp(builder, co, primals, c, argnums)
+    vg, gg = ad.vjp(builder, co, primals, c, argnums, generic_rules=True)
+    np.testing.assert_array_equal(v, value)
+    np.testing.assert_array_equal(vg, value)
+    _close(_flat(g), want, scale, name + " default rules")
+    _close(_flat(gg), want, scale, name + " generic rules")
+    _close(_flat(g), _flat(gg), scale, name + " default against generic")
+
+
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.OP_GEOMETRIES))
+def test_parameter_adjoints_of_every_op(name, engine):
+    """P̄ of every parameter of the default lowering of one geometry per rule, both paths, against forward mode."""
+    make, dim, _targets, _regions = autodiff_scenes.OP_GEOMETRIES[name]
+    geo = make(ns, *autodiff_scenes.OP_DEFAULTS)
+    low, origin = ad._lower(geo, shortcuts=True)
+    prog = ad._adjoint_program(low, origin)
+    co = _points(seed=15, n=2048, dim=dim)
+    c = np.random.default_rng(4).normal(size=co.shape[1]).astype(np.float32)
+    want, scale = _param_contraction(prog, co, c, low.params.size)
+    for generic in (False, True):
+        v, pbar, _loss = ad._reverse(prog, co, c, 0, generic, low.params.size)
+        v.free()
+        _close(pbar, want, scale, "%s generic=%s" % (name, generic))
+
+
 def _oracle_loss(builder, primals, co, target):
     f = sdf_oracle.evaluate(builder(*primals), co)
     return float(np.sum((f - target) ** 2))

@@ -22,7 +22,8 @@ def _points(seed=5, n=4096, extent=1.6, dim=3):
 
 
 def _is_2d(name):
-    return name in autodiff_scenes.AUTODIFF_SCRIPTS and name != "gradient_map_3D" or name in ("fam_2d_prims", "fam_2d_arc_segment")
+    return name in autodiff_scenes.AUTODIFF_SCRIPTS and name != "gradient_map_3D" or name in (
+        "fam_2d_prims", "fam_2d_arc_segment", "fam_triangle_smax_parameters")
 
 
 def _reference(builder, primals, a, i, co):
@@ -35,6 +36,20 @@ def _reference(builder, primals, a, i, co):
         return (f[0] - f[1]) / (2 * h)
     h = 1e-6 * max(1.0, abs(p))
     D, D8 = diff(h), diff(h / 8)
+    keep = np.abs(D - D8) <= 1e-7 * np.maximum(1.0, np.abs(D))
+    return D, keep
+
+
+def _spatial_reference(geo, co, ax):
+    """float64 central difference of the oracle along axis `ax` at h = 1e-6, and the kink filter: the points where it
+    agrees with the difference at h / 8."""
+    def moved(d):
+        c = co.copy()
+        c[ax] += d
+        return sdf_oracle.evaluate(geo, c)
+    h = 1e-6
+    D = (moved(h) - moved(-h)) / (2 * h)
+    D8 = (moved(h / 8) - moved(-h / 8)) / (h / 4)
     keep = np.abs(D - D8) <= 1e-7 * np.maximum(1.0, np.abs(D))
     return D, keep
 
@@ -167,6 +182,85 @@ def test_spatial_gradient_of_default_programs(name, engine):
         D8 = (moved(h / 8) - moved(-h / 8)) / (h / 4)
         keep = np.abs(D - D8) <= 1e-7 * np.maximum(1.0, np.abs(D))
         _check(g[ax], D, keep, "%s axis %d" % (name, ax))
+
+
+def _op_builder(name):
+    make = autodiff_scenes.OP_GEOMETRIES[name][0]
+    return lambda tx, ty, ang, s: make(ns, tx, ty, ang, s)
+
+
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.OP_GEOMETRIES))
+def test_spatial_gradient_of_every_op(name, engine):
+    """∇_x of one geometry per dual rule behind a skew placement (every input-tangent term with all components live),
+    on the default lowering, against central differences of the oracle; the value is create()'s bit for bit."""
+    _make, dim, _targets, _regions = autodiff_scenes.OP_GEOMETRIES[name]
+    geo = _op_builder(name)(*autodiff_scenes.OP_DEFAULTS)
+    co = _points(seed=15, dim=dim)
+    value, g = ad.value_and_grad_points(geo, co)
+    np.testing.assert_array_equal(value, geo.create(co))
+    for ax in range(3):
+        D, keep = _spatial_reference(geo, co, ax)
+        if dim == 2 and ax == 2:
+            assert np.all(g[ax][D == 0.0] == 0.0), "%s: the z row of a 2-D geometry" % name
+        if name in autodiff_scenes.ZERO_TANGENT_ENTRIES:
+            assert np.all(g[ax][D == 0.0] == 0.0), "%s axis %d: the tangent of a piecewise-constant map" % (name, ax)
+        _check(g[ax], D, keep, "%s axis %d" % (name, ax))
+
+
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.NORMAL_POINTS))
+def test_spatial_gradient_beside_the_normals_at_corners(name, engine):
+    """Points at 1e-4 to 3e-3 rad from the normal erected where two pieces of the boundary meet (every vertex of the
+    triangle, the rim of the cone), 0.005 to 0.5 piece lengths away, on the side of the piece with the free foot. There
+    the two pieces' squared distances tie in fp32 and their gradients differ by the angle, 30 times the bound at the most:
+    a rule that picks by the squared distance alone fails (the triangle's did, by up to 3e-3)."""
+    geo = _op_builder(name)(*autodiff_scenes.OP_DEFAULTS)
+    co = autodiff_scenes.world_coordinates(geo, autodiff_scenes.NORMAL_POINTS[name]())
+    co = co.astype(np.float32).astype(np.float64)
+    value, g = ad.value_and_grad_points(geo, co)
+    np.testing.assert_array_equal(value, geo.create(co))
+    for ax in range(3):
+        D, keep = _spatial_reference(geo, co, ax)
+        _check(g[ax], D, keep, "%s axis %d" % (name, ax))
+
+
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.OP_GEOMETRIES))
+def test_placement_jacobian_of_every_op(name, engine):
+    """d/d(tx, ty, ang, s) of the same geometries: the input-tangent terms again, through the K = 4 parameter-mode
+    instantiation, fed by XFORM's parameter tangents (one launch)."""
+    dim = autodiff_scenes.OP_GEOMETRIES[name][1]
+    builder, primals = _op_builder(name), autodiff_scenes.OP_DEFAULTS
+    co = _points(seed=15, dim=dim)
+    value, jac = ad.value_and_jacfwd(builder, co, primals, (0, 1, 2, 3))
+    assert np.all(np.isfinite(value))
+    for a, t in enumerate(jac):
+        D, keep = _reference(_op_builder(name), primals, a, None, co)
+        if name in autodiff_scenes.ZERO_TANGENT_ENTRIES:
+            assert np.all(t[D == 0.0] == 0.0), "%s argnum %d: the tangent of a piecewise-constant map" % (name, a)
+        _check(t, D, keep, "%s argnum %d" % (name, a))
+
+
+@pytest.mark.parametrize("name", sorted(autodiff_scenes.OP_GEOMETRIES))
+def test_derivatives_are_finite_on_a_grid_through_the_origin(name, engine):
+    """Identity placement and a grid with nodes exactly on the rules' ties (x == 0, |x| == |y|, the ends of the repeated
+    spans, sector boundaries): the value, ∇_x, the four-channel Jacobian and the vjp are finite for every rule. The
+    placement keeps its constant z offset, so a 3-D entry runs a second time on the grid moved by that offset, whose
+    nodes then sit on the ties in z as well (z == 0, the caps, the ends of a span along z)."""
+    dim = autodiff_scenes.OP_GEOMETRIES[name][1]
+    co, _res = ns.generate_grid((2, 2, 2), (20, 20, 20)) if dim == 3 else ns.generate_grid((2, 2), (20, 20))
+    builder, primals = _op_builder(name), autodiff_scenes.OP_IDENTITY
+    grids = [co]
+    if dim == 3:
+        moved = np.array(co, dtype=np.float64)
+        moved[2] += autodiff_scenes.PLACE_Z
+        grids.append(moved)
+    for co in grids:
+        value, g = ad.value_and_grad_points(builder(*primals), co)
+        assert np.all(np.isfinite(value)) and np.all(np.isfinite(g))
+        value, jac = ad.value_and_jacfwd(builder, co, primals, (0, 1, 2, 3))
+        assert np.all(np.isfinite(value)) and np.all(np.isfinite(np.stack(jac)))
+        c = np.random.default_rng(17).normal(size=value.size).astype(np.float32)
+        v, grads = ad.vjp(builder, co, primals, c, (0, 1, 2, 3))
+        assert np.all(np.isfinite(v)) and np.all(np.isfinite(np.array(grads, dtype=np.float64)))
 
 
 def test_no_nan_at_centres_and_axes(engine):
