@@ -143,6 +143,13 @@ SIGNATURES = {
     "sdfk_field_redistance_scratch": (_sz, [_i64, _i64, _i64]),
     "sdfk_field_redistance": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _int, _vp, _vp,
                                      _c.POINTER(_i64), _fp, _vp]),
+    "sdfk_box_pad_ulps": (_int, []),
+    "sdfk_box_has_rule": (_int, [_int]),
+    "sdfk_program_box_check": (_int, [_vp, _c.POINTER(_int)]),
+    "sdfk_enclose_boxes_device": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sdfk_enclose_octree_scratch": (_sz, []),
+    "sdfk_enclose_octree_device": (_int, [_vp, _vp, _i64, _c.POINTER(_c.c_double), _int, _c.c_float, _vp, _vp, _vp, _i64,
+                                          _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_int), _vp, _vp]),
 }
 
 

@@ -595,6 +595,38 @@ int sdfk_field_redistance(const float* d_field, const float* ax0, int64_t n0, co
                           int64_t n2, float level, float band, int near, float* d_out, void* d_scratch, int64_t* seeds,
                           float* pass_ms, void* stream);
 
+/* ---- interval enclosures (aegolius_amd.enclosure; csrc/sdfk_enclosure.inc, csrc/sdfk_boxdev.h) ------------------------
+ * An enclosure of a program over an axis-aligned box B is a pair [lo, hi] with lo <= f(p) <= hi for every fp32 point p of
+ * B, f being the fp32 field the evaluation kernels compute; an end is never NaN (a rule that cannot bound gives -inf /
+ * +inf). The rules, their padding (sdfk_box_pad_ulps() ulps of the largest magnitude a rule handles) and the contract are
+ * in csrc/sdfk_boxdev.h and DESIGN.md 4.17. d_factors: one float per instruction, DEVICE: the Lipschitz factor of a
+ * coordinate operation (+inf: none), the Lipschitz constant of a primitive, anything for value operations. */
+int sdfk_box_pad_ulps(void);
+/* 1 if the opcode has a box rule. */
+int sdfk_box_has_rule(int op);
+/* 0: every instruction has a box rule and the program fits the kernel's 16 coordinate / 8 value registers; 1: an
+ * instruction without a rule, *first_bad_op (nullable) = its index; 2: the register files are exceeded. */
+int sdfk_program_box_check(sdfk_program* prog, int* first_bad_op);
+/* n boxes: row r of the lower ends at d_lo + r * stride, r = 0, 1, 2 = x, y, z, likewise d_hi (fp32, lo <= hi, finite: not
+ * checked on the device). d_out_lo / d_out_hi: n floats each. One box per lane, every instruction evaluated. Asynchronous
+ * on `stream`. */
+int sdfk_enclose_boxes_device(sdfk_program* prog, const float* d_lo, const float* d_hi, int64_t n, int64_t stride,
+                              const float* d_factors, float* d_out_lo, float* d_out_hi, void* stream);
+/* One refinement step of an octree (dims = 3) or quadtree (dims = 2: z = 0) over `domain` = {lo x, y, z, hi x, y, z}
+ * (HOST doubles). d_keys: n box keys, level << 57 | ix << 38 | iy << 19 | iz with 0 <= i < 2^level, level <= 19. The box of
+ * a key along an axis is [lo + (hi - lo) (i / 2^level), lo + (hi - lo) ((i + 1) / 2^level)] in float64 as written (the last
+ * cell ends at hi itself), rounded outward to fp32. d_status[k] = -1 when the box is entirely inside (enclosure hi <=
+ * level), +1 entirely outside (lo > level), 0 mixed (d_status may be NULL: the counts alone). The 8 (4) children of every mixed key are appended to d_children in
+ * no particular order, never beyond `capacity` keys (capacity 0: nothing is written and d_children may be NULL);
+ * *needed = the number of children there are, so a caller whose capacity was too small learns the size to ask for.
+ * counts[3] = boxes inside, outside, mixed; hull[6] = minimum and maximum (ix, iy, iz) of the leaves that are not outside:
+ * the inside boxes and, when no child list is kept (capacity 0: the last level), the mixed ones (0x7fffffff / -1 when
+ * there are none). d_scratch: sdfk_enclose_octree_scratch() bytes. Synchronous. */
+size_t sdfk_enclose_octree_scratch(void);
+int sdfk_enclose_octree_device(sdfk_program* prog, const uint64_t* d_keys, int64_t n, const double* domain, int dims,
+                               float level, const float* d_factors, signed char* d_status, uint64_t* d_children,
+                               int64_t capacity, int64_t* needed, int64_t* counts, int* hull, void* d_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
