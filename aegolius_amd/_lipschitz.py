@@ -25,12 +25,28 @@ def _norm2(m9):
 
 
 def _neucircle(p):
+    """(|x|^o + |y|^o)^(1/o) - r: the o-norm is 1-Lipschitz for o >= 2 and 2^(1/o - 1/2)-Lipschitz for 1 <= o < 2 (its
+    ratio to the Euclidean norm on the diagonal). For o < 1 it is no norm: |x|^o has unbounded slope at the axes
+    (measured on NEUCircle(0.6, 0.5): 136 against a claim of 2.83), so there is no bound."""
     order, kind = p[1], p[2]
     if kind in (1.0, 2.0):
         return 1.0
-    if kind == 3.0 or order <= 0:
+    if kind == 3.0 or not order >= 1.0:
         return INF
     return 1.0 if order >= 2 else float(2.0 ** (1.0 / order - 0.5))
+
+
+def _quad3(p):
+    """The quad's field is the distance to the plane of its first corner inside the prism of the four edges and the
+    distance to the edges outside it: the two pieces meet only when the four vertices are coplanar. A bent quad jumps
+    across the prism's faces (measured: slope quotients above 1000), so it has no bound."""
+    a, b, c, d = p[0:3], p[3:6], p[6:9], p[9:12]
+    normal = np.cross(b - a, a - d)
+    size = max(float(np.abs(p[0:12]).max()), 1e-300)
+    norm = float(np.linalg.norm(normal))
+    if not norm > 0.0:
+        return INF
+    return 1.0 if abs(float(normal.dot(c - a))) <= 1e-9 * size * norm else INF
 
 
 # coordinate -> coordinate : factor on the coordinate constant
@@ -46,6 +62,7 @@ V_C = {name: (lambda p: 1.0) for name in (
     "P_SEGMENT2", "P_RBOX2", "P_TRIANGLE2", "P_ARC2", "P_ARC3D", "P_SECTOR", "P_INFSECTOR", "P_NGON", "P_SEGLINE2",
     "P_NEAREST2", "P_ZSLAB", "P_NEARTREE")}
 V_C["P_NEUCIRCLE"] = _neucircle
+V_C["P_QUAD3"] = _quad3
 # value -> value : factor
 V_V = {
     "VSCALE": lambda p: abs(float(p[0])), "VSUBC": lambda p: 1.0, "VAFFINE": lambda p: abs(float(p[0])),
