@@ -577,1291 +577,120 @@ extern "C" const char* sdfk_program_source(sdfk_program* p) {
     return p->source.c_str();
 }
 
-// tile geometry of the brick-culling kernel: SDFK_TWAVES waves x SDFK_WBRICKS bricks of 128 points per
-// workgroup (overridable through the environment for experiments)
-// (experiments: "-DSDFK_TWAVES=n" / "-DSDFK_RWBRICKS=n" inside the extra build switches override the launch geometry)
-static std::atomic<int> g_twaves_override{0}, g_rwbricks_override{0};
-static int tile_waves() {
-    static int v = [] { const char* e = getenv("SDFK_TWAVES"); int t = e ? atoi(e) : 4; return (t >= 1 && t <= 16) ? t : 4; }();
-    const int o = g_twaves_override.load();
-    return o ? o : v;
-}
-static int tile_wbricks() {
-    static int v = [] {
-        const char* e = getenv("SDFK_WBRICKS");
-        int t = e ? atoi(e) : 4;
-        if (t < 1 || t > 32) t = 4;
-        return t;
-    }();
-    return v;
-}
-static int tile_points() { return tile_waves() * tile_wbricks() * 128; }
-// bricks per wave of the row-block kernel: 2 — except for big trees (> 150 instructions, e.g. the 50-primitive 2-D
-// union), whose whole-tree probe is better shared by 16 bricks per workgroup than by 8 (measured -11 %)
-// waves per workgroup of the row-block kernel: 4. (Round 2 measured 2 best, when ONE lane per brick probed the whole tree and
-// a bigger workgroup only made more waves wait for it. Since the probe runs on all lanes — round 3 — the workgroup's serial
-// steps, centres and fold on the first wave, are shared by more bricks: round 4, one box, 2 -> 4 waves: north-star tree
-// 2.944 -> 2.913 ms, 20-primitive tree 3.356 -> 3.186 at 1025^3 and 25.4 -> 24.9 at 2049^3, 50-member flat union 0.847 ->
-// 0.833, 513^3 1-2 %; 3, 6 and 8 waves are slower everywhere: profiles/r04_rwaves_sweep.txt.)
-static std::atomic<int> g_rwaves_override{0};
-static int rows_waves(const sdfk_program*) {
-    if (const int o = g_rwaves_override.load()) return o;
-    return 4;
-}
-static int rows_wbricks(const sdfk_program* p);
-// Programs that are not chains and hold more than SDFK_BIG_PROGRAM instructions (300) are built with two LLVM passes off
-// (big_build_options): bit 16 of the geometry word, which selects the compiler options of a build and is part of its key
-static long long big_program_limit() {
-    static const long long v = [] {
-        const char* e = getenv("SDFK_BIG_PROGRAM");
-        const long long t = e ? atoll(e) : 300;
-        return t > 0 ? t : 300;
-    }();
-    return v;
-}
-static int rows_geo(const sdfk_program* p) {
-    const bool big = p && !p->chain_mode && (long long)(p->code.size() / 2) > big_program_limit();
-    return rows_wbricks(p) | (rows_waves(p) << 4) | (big ? 1 << 16 : 0);
-}
-static int rows_wbricks(const sdfk_program* p) {
-    static int forced = [] { const char* e = getenv("SDFK_RWBRICKS"); int t = e ? atoi(e) : 0; return (t >= 1 && t <= 16) ? t : 0; }();
-    if (const int o = g_rwbricks_override.load()) return o;
-    if (forced) return forced;
-    // chain mode (measured, 513^3 sphere unions and the 50-child flat union): every brick of a wave costs a fold and an
-    // evaluation pass one after the other, and the leaf values take 6 bytes of LDS per child and brick — few bricks per
-    // wave win: 1000 spheres 21.9 / 11.4 / 5.5 ms with 4 / 2 / 1, the flat union 1.08 / 0.99 / 1.03 ms
-    if (p && p->chain_mode) return p->chain_members <= 64 ? 2 : 1;
-    // (rounds 2-3 gave programs beyond 150 instructions 4 bricks per wave; with skip bits for every site — SDFK_MASK_SITES —
-    //  2 win at every size: 70 / 100 / 150 / 200 primitives at 513^3 1.40 / 1.87 / 2.79 / 3.51 ms against 1.55 / 2.34 / 3.18 /
-    //  4.00, profiles/r04_bigtree_wbricks.txt)
-    return 2;
-}
-struct RowGeom {           // mirrors sdfk_rowgeom of the generated source
-    unsigned L, nchunk, nbricks;
-    long long R;
-    long long row0;
-    int yrows;
-    // row blocks never straddle a PLANE of the grid (rows of one x): the slab's rows are the rest of a first plane
-    // (seg0 rows, nb0 blocks), then planes of prow rows (bpp blocks each; the last block of a plane may be partial)
-    unsigned prow, seg0, nb0, bpp;
-    unsigned inv_nchunk, inv_bpp;                              // floor(2^32 / nchunk), floor(2^32 / bpp) (sdfk_udiv)
-};
-// can the row-block kernel take n points in rows of row_len? (brick ids are 32-bit)
-// plane_rows: rows per grid plane (0 / >= R: one plane — blocks of 16 consecutive rows throughout);
-// plane_phase: index within its plane of the first row. Both are layout hints like row_len: they only decide which
-// 16 rows form a block (a block of rows from two planes has a bounding sphere as wide as the grid and culls nothing).
-static bool rows_geometry(long long n, long long row_len, RowGeom* g, long long plane_rows = 0, long long plane_phase = 0,
-                          bool planes_on = false) {
-    if (row_len < 32 || row_len > 0x7fffffffLL || n <= 0 || n % row_len != 0) return false;
-    const long long R = n / row_len, brows = 16;
-    // windows of 32 points aligned in the flat array: one more than ceil(L / 32) can overlap a row
-    const long long nchunk = (row_len % 32 == 0) ? row_len / 32 : (row_len + 62) / 32;
-    long long prow = plane_rows, seg0 = 0;
-    // Measured on 513^3 / 1025^3 (tools/rows_ab.py `noplanes:`): the partial block that ends every plane of 2^k + 1 rows
-    // costs as much as the one straddling block it replaces saves (513^3: 0.413 vs 0.401 ms, 1025^3 equal) — so the hint
-    // is honoured only on request (SDFK_PLANE_BLOCKS=1); the default is blocks of 16 consecutive rows throughout.
-    static const bool plane_blocks = [] { const char* e = getenv("SDFK_PLANE_BLOCKS"); return e && e[0] == '1'; }();
-    if (!(plane_blocks || planes_on) || prow <= 0 || prow >= R || prow > 0x7fffffffLL) {
-        prow = R > 0x7fffffffLL ? 0 : R;                       // one plane
-        if (prow == 0) return false;
-    } else if (plane_phase > 0) {
-        seg0 = std::min(R, (prow - plane_phase % prow) % prow);
-    }
-    const long long nb0 = (seg0 + brows - 1) / brows, bpp = (prow + brows - 1) / brows;
-    const long long planes = (R - seg0 + prow - 1) / prow;
-    const long long nb = nchunk * (nb0 + planes * bpp);
-    if (nb > 0x7fffffffLL - 1024) return false;
-    g->L = (unsigned)row_len;
-    g->nchunk = (unsigned)nchunk;
-    g->nbricks = (unsigned)nb;
-    g->R = R;
-    g->row0 = 0;
-    g->yrows = 0;
-    g->prow = (unsigned)prow;
-    g->seg0 = (unsigned)seg0;
-    g->nb0 = (unsigned)nb0;
-    g->bpp = (unsigned)bpp;
-    g->inv_nchunk = (unsigned)std::min<unsigned long long>(0xffffffffull, (1ull << 32) / (unsigned long long)nchunk);
-    g->inv_bpp = (unsigned)std::min<unsigned long long>(0xffffffffull, (1ull << 32) / (unsigned long long)bpp);
-    return true;
-}
-static int tile_threads() { return 64 * tile_waves(); }
-// On-disk cache of hiprtc code objects, ON by default: a new process loads the kernels of tree / chain shapes it has
-// seen before instead of compiling them. Directory: $SDFK_CACHE_DIR, else $XDG_CACHE_HOME/sdfk, else $HOME/.cache/sdfk;
-// SDFK_CACHE_DIR= (empty), "off" or "0" disables it. The file name is a 64-bit FNV-1a hash of the source, the options
-// and the hiprtc version, plus the source length. A cache that cannot be created, read or written is never an error.
-static std::string rtc_cache_dir() {
-    static const std::string dir = [] {
-        std::string d;
-        if (const char* e = getenv("SDFK_CACHE_DIR")) {
-            d = e;
-            if (d.empty() || d == "off" || d == "0") return std::string();
-        } else if (const char* x = getenv("XDG_CACHE_HOME"); x && *x) {
-            d = std::string(x) + "/sdfk";
-        } else if (const char* h = getenv("HOME"); h && *h) {
-            (void)mkdir((std::string(h) + "/.cache").c_str(), 0700);
-            d = std::string(h) + "/.cache/sdfk";
-        } else {
-            return std::string();
-        }
-        (void)mkdir(d.c_str(), 0700);
-        return d;
-    }();
-    return dir;
-}
-static std::string rtc_cache_path(const std::string& src, const std::string& opts) {
-    const std::string dir = rtc_cache_dir();
-    if (dir.empty()) return std::string();
-    int major = 0, minor = 0;
-    (void)hiprtcVersion(&major, &minor);
-    unsigned long long h = 1469598103934665603ull;
-    auto mix = [&](const std::string& t) {
-        for (unsigned char c : t) {
-            h ^= c;
-            h *= 1099511628211ull;
-        }
-    };
-    mix(src);
-    mix(opts);
-    mix(std::to_string(major) + "." + std::to_string(minor) + "/abi" + std::to_string(SDFK_ABI_VERSION));
-    char name[96];
-    snprintf(name, sizeof name, "/sdfk-%016llx-%zu.co", h, src.size());
-    return dir + name;
-}
-// File = code object + 24-byte trailer {magic, payload length, FNV-1a of the payload}: a truncated or foreign file is
-// never handed to hipModuleLoadData (it is deleted instead).
-static const unsigned long long kCacheMagic = 0x53444643'4f424a31ull;           // "SDFCOBJ1"
-static unsigned long long fnv1a(const char* p, size_t n) {
-    unsigned long long h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) {
-        h ^= (unsigned char)p[i];
-        h *= 1099511628211ull;
-    }
-    return h;
-}
-static bool rtc_cache_read(const std::string& path, std::vector<char>* out) {
-    if (path.empty()) return false;
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    bool ok = false;
-    if (fseek(f, 0, SEEK_END) == 0) {
-        const long size = ftell(f);
-        if (size > 24 && fseek(f, 0, SEEK_SET) == 0) {
-            out->resize((size_t)size);
-            ok = fread(out->data(), 1, (size_t)size, f) == (size_t)size;
-            if (ok) {
-                unsigned long long tr[3];
-                memcpy(tr, out->data() + size - 24, 24);
-                ok = tr[0] == kCacheMagic && tr[1] == (unsigned long long)(size - 24) && tr[2] == fnv1a(out->data(), (size_t)size - 24);
-                out->resize((size_t)size - 24);
-            }
-        }
-    }
-    fclose(f);
-    if (!ok) {
-        out->clear();
-        (void)remove(path.c_str());                            // truncated / corrupt / older format: rebuilt and rewritten
-    } else {
-        (void)utimes(path.c_str(), nullptr);                   // most recently used (the eviction below goes by mtime)
-    }
-    return ok;
-}
-// keep the directory below SDFK_CACHE_MAX_MB (default 512): oldest files go first, down to three quarters of the cap
-static void rtc_cache_evict(const std::string& dir) {
-    static const long long cap = [] {
-        const char* e = getenv("SDFK_CACHE_MAX_MB");
-        const long long v = e ? atoll(e) : 512;
-        return (v > 0 ? v : 512) * (1ll << 20);
-    }();
-    DIR* d = opendir(dir.c_str());
-    if (!d) return;
-    std::vector<std::pair<long long, std::pair<std::string, long long>>> files;   // (mtime, (path, size))
-    long long total = 0;
-    while (dirent* e = readdir(d)) {
-        const std::string name = e->d_name;
-        if (name.compare(0, 5, "sdfk-") != 0 || name.compare(0, 9, "sdfk-rtc-") == 0) continue;   // (not the hand-over directories of builds in flight)
-        struct stat st;
-        const std::string path = dir + "/" + name;
-        if (stat(path.c_str(), &st) != 0) continue;
-        total += (long long)st.st_size;
-        files.push_back({(long long)st.st_mtime, {path, (long long)st.st_size}});
-    }
-    closedir(d);
-    if (total <= cap) return;
-    std::sort(files.begin(), files.end());
-    for (const auto& f : files) {
-        if (total <= cap / 4 * 3) break;
-        if (remove(f.second.first.c_str()) == 0) total -= f.second.second;
-    }
-}
-static void rtc_cache_write(const std::string& path, const std::vector<char>& co) {
-    if (path.empty() || co.empty()) return;
-    const std::string tmp = path + ".tmp" + std::to_string((long long)getpid());
-    FILE* f = fopen(tmp.c_str(), "wb");
-    if (!f) return;                                            // a cache that cannot be written is no error
-    const unsigned long long tr[3] = {kCacheMagic, (unsigned long long)co.size(), fnv1a(co.data(), co.size())};
-    bool ok = fwrite(co.data(), 1, co.size(), f) == co.size() && fwrite(tr, 1, sizeof tr, f) == sizeof tr;
-    ok = (fclose(f) == 0) && ok;                               // (a short write on a full disk may only show here)
-    if (!ok || rename(tmp.c_str(), path.c_str()) != 0) (void)remove(tmp.c_str());   // atomic: readers never see a partial file
-    else rtc_cache_evict(rtc_cache_dir());
-}
+// launch geometry that the build options and the keys of code objects depend on (sdfk_launch.inc)
+static int tile_waves();
+static int tile_wbricks();
+static int rows_geo(const sdfk_program* p);
+#include "sdfk_jit.inc"
+#include "sdfk_launch.inc"
 
-static std::mutex g_rtc_mu;   // hiprtc and hipModuleLoadData: one thread at a time (see BuildWorker)
-// extra -D switches for the generated source (experiments): SDFK_RTC_DEFS="-DSDFK_TWAVES=2 ..." or sdfk_debug_set_rtc_defs
-static std::mutex g_defs_mu;
-static std::string g_rtc_defs = [] { const char* e = getenv("SDFK_RTC_DEFS"); return std::string(e ? e : ""); }();
-extern "C" void sdfk_debug_set_rtc_defs(const char* defs) {
-    std::lock_guard<std::mutex> lk(g_defs_mu);
-    std::string rest;
-    int tw = 0, rwb = 0, rwv = 0;
-    const std::string all = defs ? defs : "";
-    size_t pos = 0;
-    while (pos < all.size()) {
-        size_t sp = all.find(' ', pos);
-        if (sp == std::string::npos) sp = all.size();
-        const std::string tok = all.substr(pos, sp - pos);
-        if (tok.compare(0, 14, "-DSDFK_TWAVES=") == 0) tw = atoi(tok.c_str() + 14);
-        else if (tok.compare(0, 16, "-DSDFK_RWBRICKS=") == 0) rwb = atoi(tok.c_str() + 16);
-        else if (tok.compare(0, 14, "-DSDFK_RWAVES=") == 0) rwv = atoi(tok.c_str() + 14);
-        else if (!tok.empty()) rest += tok + " ";
-        pos = sp + 1;
-    }
-    g_twaves_override = (tw >= 1 && tw <= 16) ? tw : 0;
-    g_rwbricks_override = (rwb >= 1 && rwb <= 15) ? rwb : 0;
-    g_rwaves_override = (rwv >= 1 && rwv <= 16) ? rwv : 0;
-    g_rtc_defs = rest;
-}
-// geo: bricks per wave | waves per workgroup << 4 of the row-block kernel (rows_geo)
-static std::vector<std::string> rtc_options(int geo) {
-    const int rwb = geo & 15, rwaves = ((geo >> 4) & 0xff) ? ((geo >> 4) & 0xff) : 4;
-    const bool big = (geo >> 16) & 1;
-    const char* opt = getenv("SDFK_RTC_OPT");                 // experiments: "-O1" ... (the cache key carries the options)
-    std::vector<std::string> o = {"--offload-arch=gfx950", (opt && opt[0] == '-') ? opt : "-O3", "-ffp-contract=off", "-std=c++17",
-                                  // -fno-honor-nans: v_min/v_max without the canonicalising pre-op. -mno-amdgpu-ieee (same
-                                  // flags as the hipcc build of the interpreter kernel: both flavours stay bit-identical)
-                                  // keeps the device library's sincos / atan2 / pow out of line — the inliner refuses
-                                  // across the attribute — which is what a 50-primitive 2-D tree wants: 296 KB of code
-                                  // instead of 490 KB, 10 s of compile instead of 15 s, 1.19 vs 1.22 ms at 16385^2
-                                  "-fno-honor-nans", "-mno-amdgpu-ieee",
-                                  "-DSDFK_TWAVES=" + std::to_string(tile_waves()), "-DSDFK_WBRICKS=" + std::to_string(tile_wbricks()),
-                                  "-DSDFK_RWBRICKS=" + std::to_string(rwb), "-DSDFK_RWAVES=" + std::to_string(rwaves)};
-    if (big) {
-        // Big programs (round 4): hiprtc's time grows with the square of a straight-line program, and -ftime-report on a
-        // 599-instruction tree names the pass: CodeGenPrepare, 458 of 630 s (then VectorCombine, 31 of the remaining 151).
-        // Without the two a row-block build takes 30 s instead of 250 at 599 instructions, line bricks 33 s at 1199
-        // instead of 105 (profiles/r04_build_time.txt). CodeGenPrepare is worth 2 % on the north-star tree and 12 % on the
-        // 20-primitive one (profiles/r04_nocgp.txt) — so small programs keep it — but a culled kernel without it is still
-        // several times the interpreter kernel, which is what served these programs before. Same FP semantics: same bits.
-        o.push_back("-mllvm");
-        o.push_back("-disable-cgp");
-        o.push_back("-mllvm");
-        o.push_back("-disable-vector-combine");
-    }
-    if (const char* extra = getenv("SDFK_RTC_EXTRA")) {       // experiments: raw compiler options, space-separated
-        std::string e = extra;
-        size_t q = 0;
-        while (q < e.size()) {
-            size_t sp = e.find(' ', q);
-            if (sp == std::string::npos) sp = e.size();
-            if (sp > q) o.push_back(e.substr(q, sp - q));
-            q = sp + 1;
-        }
-    }
-    std::string all;
-    {
-        std::lock_guard<std::mutex> lk(g_defs_mu);
-        all = g_rtc_defs;
-    }
-    size_t pos = 0;
-    while (pos < all.size()) {
-        size_t sp = all.find(' ', pos);
-        if (sp == std::string::npos) sp = all.size();
-        if (sp > pos && all.compare(pos, 2, "-D") == 0) o.push_back(all.substr(pos, sp - pos));
-        pos = sp + 1;
-    }
-    return o;
-}
-static std::string rtc_option_key(int rwb) {
-    std::string k;
-    for (const std::string& o : rtc_options(rwb)) k += o + " ";
-    return k;
-}
-static int rtc_compile_uncached(const std::string& src, std::vector<char>* out, std::string* log, int rwb) {
-    hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "sdfk_spec.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
-        *log = "hiprtcCreateProgram failed";
-        return -1;
-    }
-    const std::vector<std::string> o = rtc_options(rwb);
-    std::vector<const char*> opts;
-    for (const std::string& x : o) opts.push_back(x.c_str());
-    hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-    size_t ls = 0;
-    hiprtcGetProgramLogSize(prog, &ls);
-    if (ls > 1) {
-        log->resize(ls);
-        hiprtcGetProgramLog(prog, &(*log)[0]);
-    }
-    if (r != HIPRTC_SUCCESS) {
-        *log = std::string("hiprtc: ") + hiprtcGetErrorString(r) + "\n" + *log;
-        hiprtcDestroyProgram(&prog);
-        return -1;
-    }
-    size_t cs = 0;
-    hiprtcGetCodeSize(prog, &cs);
-    out->resize(cs);
-    hiprtcGetCode(prog, out->data());
-    hiprtcDestroyProgram(&prog);
-    return 0;
-}
-// ---- hiprtc in a child process (background builds) -------------------------------------------------------------------
-// hiprtcCompileProgram holds comgr's process-wide mutex for the whole build; a dlopen of any library with HIP fat
-// binaries on another thread of the same process (`import torch`) deadlocks against it — loader lock -> comgr mutex there,
-// comgr mutex -> loader lock here (profiles/r03_hang_import_during_build.txt). Builds that run BESIDE the caller
-// therefore run in aegolius_amd/sdfk_rtc_helper (csrc/sdfk_rtc_helper.c): no GPU, no shared lock. Builds the caller
-// waits for stay in-process (the caller cannot dlopen while it waits). No helper next to the library: no background
-// builds — the call waits.
-extern char** environ;
-static std::string rtc_helper_path() {
-    static const std::string path = [] {
-        if (const char* e = getenv("SDFK_RTC_HELPER")) return std::string(strcmp(e, "off") && strcmp(e, "0") ? e : "");
-        Dl_info info;
-        if (!dladdr((void*)&sdfk_abi_version, &info) || !info.dli_fname) return std::string();
-        std::string p = info.dli_fname;
-        const size_t slash = p.rfind('/');
-        p = (slash == std::string::npos ? std::string(".") : p.substr(0, slash)) + "/sdfk_rtc_helper";
-        return access(p.c_str(), X_OK) == 0 ? p : std::string();
-    }();
-    return path;
-}
-static std::string rtc_library_path() {                        // the hiprtc THIS process uses (torch's or the system's)
-    Dl_info info;
-    if (!dladdr((void*)&hiprtcCompileProgram, &info) || !info.dli_fname) return std::string();
-    return info.dli_fname;
-}
-static bool rtc_helper_available() { return !rtc_helper_path().empty() && !rtc_library_path().empty(); }
-static std::atomic<bool> g_cancel_builds{false};              // set by sdfk_jit_cancel: running compiler children are killed, queued builds dropped
-static int rtc_compile_external(const std::string& src, std::vector<char>* out, std::string* log, int rwb) {
-    static std::atomic<unsigned> serial{0};
-    const std::string helper = rtc_helper_path(), lib = rtc_library_path();
-    if (helper.empty() || lib.empty()) {
-        *log = "sdfk_rtc_helper is not available";
-        return -2;
-    }
-    std::string dir = rtc_cache_dir();
-    if (dir.empty()) {
-        const char* t = getenv("TMPDIR");
-        dir = (t && *t) ? t : "/tmp";
-    }
-    // the hand-over files live in a directory of their own that mkdtemp creates (mode 0700, unpredictable name): nobody
-    // can plant a file or a link where the source is written or the code object is read, two processes with the same pid in
-    // different namespaces that share the cache directory cannot meet, and the cache eviction skips the "sdfk-rtc-" prefix
-    (void)serial;
-    std::string priv = dir + "/sdfk-rtc-XXXXXX";
-    if (!mkdtemp(&priv[0])) {
-        *log = "cannot create a private directory under " + dir + ": " + strerror(errno);
-        return -2;
-    }
-    const std::string srcf = priv + "/src.hip", outf = priv + "/out.co";
-    auto cleanup = [&] {
-        (void)remove(srcf.c_str());
-        (void)remove(outf.c_str());
-        (void)remove((outf + ".tmp").c_str());
-        (void)remove((outf + ".log").c_str());
-        (void)rmdir(priv.c_str());
-    };
-    {
-        const int fd = open(srcf.c_str(), O_WRONLY | O_CREAT | O_EXCL | O_CLOEXEC, 0600);
-        FILE* f = fd >= 0 ? fdopen(fd, "wb") : nullptr;
-        if (!f && fd >= 0) close(fd);
-        const bool ok = f && fwrite(src.data(), 1, src.size(), f) == src.size();
-        if (!f || fclose(f) != 0 || !ok) {
-            cleanup();
-            *log = "cannot write " + srcf;
-            return -2;
-        }
-    }
-    const std::vector<std::string> o = rtc_options(rwb);
-    std::vector<char*> argv = {const_cast<char*>(helper.c_str()), const_cast<char*>(lib.c_str()), const_cast<char*>(srcf.c_str()),
-                               const_cast<char*>(outf.c_str())};
-    for (const std::string& x : o) argv.push_back(const_cast<char*>(x.c_str()));
-    argv.push_back(nullptr);
-    posix_spawn_file_actions_t fa;
-    posix_spawn_file_actions_init(&fa);
-    posix_spawn_file_actions_addclosefrom_np(&fa, 3);          // the child inherits nothing of the GPU runtime's
-    pid_t pid = 0;
-    const int rc = posix_spawn(&pid, helper.c_str(), &fa, nullptr, argv.data(), environ);
-    posix_spawn_file_actions_destroy(&fa);
-    if (rc != 0) {
-        cleanup();
-        *log = std::string("posix_spawn of sdfk_rtc_helper: ") + strerror(rc);
-        return -2;
-    }
-    // a compiler that never returns (wedged inside comgr, a stale network file system) must not hold its worker thread —
-    // and with it sdfk_jit_drain at interpreter exit — for ever: SDFK_RTC_TIMEOUT seconds (default 900), then it is killed
-    static const double limit_s = [] { const char* e = getenv("SDFK_RTC_TIMEOUT"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 900.0; }();
-    int status = 0;
-    bool timed_out = false, cancelled = false;
-    const auto t_spawn = std::chrono::steady_clock::now();
-    for (;;) {
-        const pid_t w = waitpid(pid, &status, WNOHANG);
-        if (w == pid) break;
-        if (w < 0 && errno != EINTR) { status = -1; break; }
-        if (g_cancel_builds.load(std::memory_order_relaxed)) {  // the process is leaving (sdfk_jit_cancel): nobody will use the kernel
-            cancelled = true;
-            (void)kill(pid, SIGKILL);
-            while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {
-            }
-            break;
-        }
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_spawn).count() > limit_s) {
-            timed_out = true;
-            (void)kill(pid, SIGKILL);
-            while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {
-            }
-            break;
-        }
-        std::this_thread::sleep_for(std::chrono::milliseconds(5));
-    }
-    int result = -1;
-    if (cancelled) {
-        *log = "build cancelled: the process is shutting down";
-    } else if (timed_out) {
-        *log = "sdfk_rtc_helper did not finish within " + std::to_string((long long)limit_s) + " s (SDFK_RTC_TIMEOUT) and was killed";
-    } else if (WIFEXITED(status) && WEXITSTATUS(status) == 0) {
-        FILE* f = fopen(outf.c_str(), "rb");
-        if (f && fseek(f, 0, SEEK_END) == 0) {
-            const long size = ftell(f);
-            if (size > 0 && fseek(f, 0, SEEK_SET) == 0) {
-                out->resize((size_t)size);
-                if (fread(out->data(), 1, (size_t)size, f) == (size_t)size) result = 0;
-            }
-        }
-        if (f) fclose(f);
-        if (result) *log = "sdfk_rtc_helper left no code object";
-    } else {
-        *log = "sdfk_rtc_helper failed (status " + std::to_string(status) + ")";
-        if (FILE* f = fopen((outf + ".log").c_str(), "rb")) {
-            char buf[8192];
-            const size_t n = fread(buf, 1, sizeof buf - 1, f);
-            buf[n] = 0;
-            *log += std::string(": ") + buf;
-            fclose(f);
-        }
-    }
-    cleanup();
-    return result;
-}
-
-// *from_disk (optional): the code object came from the on-disk cache
-static int rtc_compile(const std::string& src, std::vector<char>* out, std::string* log, int rwb, bool* from_disk = nullptr,
-                       std::string* disk_path = nullptr, bool external = false) {
-    if (from_disk) *from_disk = false;
-    const std::string path = rtc_cache_path(src, rtc_option_key(rwb));
-    if (rtc_cache_read(path, out)) {
-        if (from_disk) *from_disk = true;
-        if (disk_path) *disk_path = path;
-        return 0;
-    }
-    // Builds run in the compiler CHILD process whenever it is there — the background ones (never hiprtc inside this process
-    // while the caller is free to dlopen something: profiles/r03_hang_import_during_build.txt) and the ones the caller waits
-    // for alike (ctypes releases the GIL during the wait: another Python thread that imports a HIP library would meet the same
-    // lock inversion). In-process hiprtc is the last resort, and says so once.
-    int rc = -2;
-    if (rtc_helper_available()) rc = rtc_compile_external(src, out, log, rwb);
-    if (rc == -2 && !external) {
-        static std::atomic<bool> told{false};
-        if (!told.exchange(true))
-            fprintf(stderr, "[sdfk] compiler helper unavailable (%s): building inside this process — do not import HIP libraries on "
-                            "other threads meanwhile\n", log->empty() ? "sdfk_rtc_helper not found next to libsdfk.so" : log->c_str());
-        std::lock_guard<std::mutex> lk(g_rtc_mu);
-        rc = rtc_compile_uncached(src, out, log, rwb);
-    }
-    if (rc == 0) rtc_cache_write(path, *out);
-    return rc;
-}
-
-// ---- code objects (per process) and modules (per device) -----------------------------------------
-static const char* const kFlavourFn[SDFK_FL_COUNT][2] = {
-    {"sdfk_spec_v4", "sdfk_spec_v1"}, {"sdfk_spec_g4", "sdfk_spec_g1"}, {"sdfk_spec_t", nullptr}, {"sdfk_spec_tg", nullptr},
-    {"sdfk_spec_tmask", nullptr},     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr}, {"sdfk_spec_rmask", nullptr},
-    {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr},        {"sdfk_spec_rays", "sdfk_spec_raycam"},
-    {"sdfk_spec_occ_list", "sdfk_spec_occ_all"}};
-
-// hiprtc is entered by ONE thread at a time, and never while a code object is being loaded (hipModuleLoadData):
-// g_rtc_mu. Background builds are queued to one worker thread, which is drained before the interpreter / the
-// library's statics (and with them hiprtc) go away: sdfk_jit_drain (Python: atexit) and the destructor below.
-struct BuildWorker {
-    static constexpr int kThreads = 2;                       // compiler processes that may run side by side
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::function<void()>> jobs;
-    std::vector<std::thread> threads;
-    bool stop = false;
-    int busy = 0;
-    void post(std::function<void()> job) {
-        std::lock_guard<std::mutex> lk(mu);
-        jobs.push_back(std::move(job));
-        if ((int)threads.size() < kThreads && (int)threads.size() < busy + (int)jobs.size())
-            threads.emplace_back([this] { loop(); });
-        cv.notify_all();
-    }
-    void loop() {
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            cv.wait(lk, [this] { return stop || !jobs.empty(); });
-            if (jobs.empty()) return;                        // (stop: the queue is finished first)
-            std::function<void()> job = std::move(jobs.front());
-            jobs.pop_front();
-            ++busy;
-            lk.unlock();
-            job();
-            lk.lock();
-            --busy;
-            cv.notify_all();
-        }
-    }
-    void drain() {                                           // wait until nothing is queued or running
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [this] { return jobs.empty() && busy == 0; });
-    }
-    void drop_queued() {
-        std::lock_guard<std::mutex> lk(mu);
-        jobs.clear();
-        cv.notify_all();
-    }
-    ~BuildWorker() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        for (std::thread& t : threads)
-            if (t.joinable()) t.join();
-    }
-};
-static BuildWorker g_builds;
-extern "C" void sdfk_jit_drain(void) { g_builds.drain(); }
-// At interpreter exit: a background build nobody will use any more (a big tree evaluated once: up to a minute of hiprtc)
-// must not hold the process. Queued builds are dropped, running compiler children killed, then the workers are idle.
-extern "C" void sdfk_jit_cancel(void) {
-    g_cancel_builds.store(true);
-    g_builds.drop_queued();
-    g_builds.drain();
-}
-static std::atomic<long long> g_compile_count{0};             // hiprtc builds this process has actually run
-static std::atomic<long long> g_compile_micros{0};
-extern "C" void sdfk_debug_jit_stats(int64_t* builds, double* seconds) {
-    if (builds) *builds = g_compile_count.load();
-    if (seconds) *seconds = (double)g_compile_micros.load() * 1e-6;
-}
-
-static std::shared_ptr<CodeObject> code_entry(const std::string& key) {
-    std::lock_guard<std::mutex> lk(g_code_mu);
-    std::shared_ptr<CodeObject>& e = g_code[key];
-    if (!e) e = std::make_shared<CodeObject>();
-    return e;
-}
-// run one build; the caller has moved the entry to state 1
-static void code_build(const std::shared_ptr<CodeObject>& e, const std::string& src, int rwb, bool external = false) {
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<char> co;
-    std::string log;
-    bool from_disk = false;
-    std::string disk_path;
-    const int rc = rtc_compile(src, &co, &log, rwb, &from_disk, &disk_path, external);
-    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!from_disk) {
-        g_compile_count++;
-        g_compile_micros += (long long)(dt * 1e6);
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    e->build_seconds = dt;
-    if (rc == 0) {
-        e->co.swap(co);
-        e->disk_path = disk_path;
-        e->state = 2;
-    } else {
-        e->error = log;
-        e->state = 3;
-        e->failed_at = std::chrono::steady_clock::now();
-    }
-    e->cv.notify_all();
-}
-// The code object of (source, options): wait = build here (or wait for the thread that is building); !wait = make sure
-// a build is under way (background thread) and return at once. A failed build is retried after 30 s at the earliest.
-template <typename MakeSource>
-static std::shared_ptr<CodeObject> code_get(const std::string& key, MakeSource make_source, int rwb, bool wait) {
-    std::shared_ptr<CodeObject> e = code_entry(key);
-    std::unique_lock<std::mutex> lk(e->mu);
-    if (e->state == 3 && std::chrono::steady_clock::now() - e->failed_at > std::chrono::seconds(30)) e->state = 0;
-    if (e->state == 0) {
-        e->state = 1;
-        lk.unlock();
-        const std::string src = make_source();                 // (the program may be gone before a background build ends)
-        if (wait || !rtc_helper_available()) {                 // no compiler process to hand the build to: the caller waits
-            code_build(e, src, rwb);
-        } else {
-            g_builds.post([e, src, rwb] { code_build(e, src, rwb, true); });
-        }
-        return e;
-    }
-    if (wait) e->cv.wait(lk, [&] { return e->state != 1; });
-    return e;
-}
-// with_flags: the build of a flavour that writes one flag bit per point (value <= threshold) instead of the field — a
-// translation unit of its own (#define SDFK_FLAGS), so the field kernels carry none of it.
-// with_flags is a set of build VARIANTS: bit 0 = flag-writing build (SDFK_FLAGS), bit 1 = two-row coordinates, z = 0 by
-// contract (SDFK_XY: the array kernels never read a third row — sdfk_eval_device_rows2d_xy)
-static std::string flavour_key(const sdfk_program* p, int flavour, int rwb, int with_flags = 0) {
-    return p->key + "|f" + std::to_string(flavour) + ((with_flags & 1) ? "s" : "") + ((with_flags & 2) ? "x" : "") + "|" + rtc_option_key(rwb);
-}
-static std::string flavour_source(const sdfk_program* p, int flavour, int with_flags = 0) {
-    return std::string((with_flags & 1) ? "#define SDFK_FLAGS 1\n" : "") + ((with_flags & 2) ? "#define SDFK_XY 1\n" : "") +
-           sdfk_generate_source(g_ops, SDFK_OP_COUNT, p->code.data(), p->code.size() / 2, p->result_reg, p->sites, flavour,
-                                &p->sites_all);
-}
-
-extern "C" int sdfk_program_chain_members(const sdfk_program* p) {
-    return p && p->chain_mode ? p->chain_members : 0;
-}
-extern "C" int sdfk_program_compile_check(sdfk_program* p, size_t* code_size) {
-    // every flavour this program can be launched with, each as its own translation unit (what a run would build)
-    if (!p) return fail(-1, "null program");
-    size_t total = 0;
-    const int rwb = rows_geo(p);
-    for (int f = 0; f < SDFK_FL_COUNT; ++f) {
-        if (f == SDFK_FL_RAYS) continue;                        // (not an evaluation flavour: built by the first ray cast)
-        if (f == SDFK_FL_OCCUPANCY) continue;                   // (nor this one: built by the first occupancy call)
-        if (p->sites.empty() && f != SDFK_FL_PLAIN_ARRAY && f != SDFK_FL_PLAIN_GRID) continue;
-        if (p->chain_mode && (f == SDFK_FL_TILE_ARRAY || f == SDFK_FL_TILE_GRID || f == SDFK_FL_TILE_MASK || f == SDFK_FL_ROWS_MASK)) continue;
-        std::shared_ptr<CodeObject> e = code_get(flavour_key(p, f, rwb), [&] { return flavour_source(p, f); }, rwb, true);
-        if (e->state != 2) return fail(-3, e->error);
-        total += e->co.size();
-    }
-    if (code_size) *code_size = total;
-    return 0;
-}
-/* Build (or fetch) ONE flavour without a GPU: 0 + seconds the build took (0 when it was already there). */
-extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t* code_size, double* seconds) {
-    if (!p) return fail(-1, "null program");
-    int with_flags = 0;                                                              // build variants (see flavour_key)
-    if (flavour >= 0 && (flavour & SDFK_FLAVOUR_FLAGS)) with_flags |= 1;             // the flag-writing build of the flavour
-    if (flavour >= 0 && (flavour & SDFK_FLAVOUR_XY)) with_flags |= 2;                // two-row coordinates
-    if (flavour >= 0) flavour &= ~(SDFK_FLAVOUR_FLAGS | SDFK_FLAVOUR_XY);
-    if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_program_compile_flavour: unknown flavour");
-    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY)
-        return fail(-2, "sdfk_program_compile_flavour: the program has no cull sites");
-    if (with_flags && flavour == SDFK_FL_RAYS)
-        return fail(-2, "sdfk_program_compile_flavour: the ray flavour has no flag-writing or two-row build");
-    if (with_flags && flavour == SDFK_FL_OCCUPANCY)
-        return fail(-2, "sdfk_program_compile_flavour: the occupancy flavour has no flag-writing or two-row build");
-    if ((with_flags & 2) && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_ROWS2D_ARRAY)
-        return fail(-2, "sdfk_program_compile_flavour: two-row coordinates exist for the plain and the flat row-block array kernels");
-    if ((with_flags & 1) && (flavour == SDFK_FL_TILE_ARRAY || flavour == SDFK_FL_TILE_GRID || flavour == SDFK_FL_TILE_MASK ||
-                       flavour == SDFK_FL_ROWS_MASK))
-        return fail(-2, "sdfk_program_compile_flavour: this flavour has no flag-writing build");
-    const int rwb = rows_geo(p);
-    const auto t0 = std::chrono::steady_clock::now();
-    std::shared_ptr<CodeObject> e =
-        code_get(flavour_key(p, flavour, rwb, with_flags), [&] { return flavour_source(p, flavour, with_flags); }, rwb, true);
-    if (e->state != 2) return fail(-3, e->error);
-    if (code_size) *code_size = e->co.size();
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return 0;
-}
-
-/* Test aid: build one flavour in the compiler child process (what a background build does), GPU or not. */
-extern "C" int sdfk_debug_compile_external(sdfk_program* p, int flavour, size_t* code_size) {
-    if (!p) return fail(-1, "null program");
-    if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_debug_compile_external: unknown flavour");
-    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY)
-        return fail(-2, "sdfk_debug_compile_external: the program has no cull sites");
-    if (!rtc_helper_available()) return fail(-9, "sdfk_rtc_helper is not next to libsdfk.so (or hiprtc cannot be located)");
-    std::vector<char> co;
-    std::string log;
-    if (rtc_compile_external(flavour_source(p, flavour), &co, &log, rows_geo(p)) != 0) return fail(-3, log);
-    if (code_size) *code_size = co.size();
-    return 0;
-}
-
-// The module of one flavour on one device. wait = false: nullptr while the code object is still being built in the
-// background (the caller serves this call from the interpreter kernel — same bits). *err is set on failure.
-static std::shared_ptr<SpecModule> get_module(sdfk_program* p, int device, int flavour, bool wait, std::string* err,
-                                              int with_flags = 0) {
-    const int rwb = rows_geo(p);
-    const std::string key = flavour_key(p, flavour, rwb, with_flags);
-    std::shared_ptr<SpecModule> m;
-    {
-        std::lock_guard<std::mutex> lk(g_code_mu);
-        std::shared_ptr<SpecModule>& slot = g_mods[std::make_pair(device, key)];
-        if (!slot) slot = std::make_shared<SpecModule>();
-        m = slot;
-    }
-    std::lock_guard<std::mutex> lk(m->mu);                     // per (device, flavour): loads never block other devices
-    if (m->loaded) return m;
-    for (int attempt = 0;; ++attempt) {
-        std::shared_ptr<CodeObject> e;
-        {
-            std::lock_guard<std::mutex> ce(g_code_mu);
-            auto it = g_code.find(key);
-            if (it != g_code.end()) e = it->second;
-        }
-        int state = 0;
-        if (e) {
-            std::lock_guard<std::mutex> el(e->mu);
-            state = e->state;
-        }
-        if (state != 2) {
-            e = code_get(key, [&] { return flavour_source(p, flavour, with_flags); }, rwb, wait);
-            std::lock_guard<std::mutex> el(e->mu);
-            state = e->state;
-        }
-        if (state == 1) return nullptr;                            // still building (wait == false)
-        if (state != 2) {
-            std::lock_guard<std::mutex> el(e->mu);
-            *err = e->error;
-            m->failed = true;
-            m->error = e->error;
-            return m;                                              // (not marked loaded: a later call asks code_get again)
-        }
-        hipError_t he;
-        {
-            std::lock_guard<std::mutex> rl(g_rtc_mu);
-            he = hipModuleLoadData(&m->mod, e->co.data());
-        }
-        for (int i = 0; i < 2 && he == hipSuccess; ++i)
-            if (kFlavourFn[flavour][i]) he = hipModuleGetFunction(&m->fn[i], m->mod, kFlavourFn[flavour][i]);
-        if (he == hipSuccess && p->chain_mode && !kFlavourFn[flavour][1]) {
-            // chain-mode row-block kernels come with the pre-pass of their candidate lists (absent from -DSDFK_NO_CELLS builds)
-            const bool grid_fl = flavour == SDFK_FL_ROWS_GRID || flavour == SDFK_FL_ROWS2D_GRID;
-            if (hipModuleGetFunction(&m->fn[1], m->mod, grid_fl ? "sdfk_spec_cellsg" : "sdfk_spec_cells") != hipSuccess) {
-                m->fn[1] = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        if (he == hipSuccess && flavour == SDFK_FL_RAYS) {
-            // long chains come with a second pair of kernels that cull along the rays (sdfk_codegen.cpp: kRaysCull)
-            if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_rays_cull") != hipSuccess ||
-                hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_raycam_cull") != hipSuccess) {
-                m->fn[2] = m->fn[3] = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        if (he == hipSuccess) break;
-        // A code object that came from the on-disk cache and does not load (another driver / compiler generation, a
-        // damaged file that still passed the checksum): delete the file, forget the blob and build from source once.
-        bool retry = false;
-        {
-            std::lock_guard<std::mutex> el(e->mu);
-            if (attempt == 0 && e->state == 2 && !e->disk_path.empty()) {
-                (void)remove(e->disk_path.c_str());
-                fprintf(stderr, "[sdfk] cached code object %s does not load (%s): rebuilding\n", e->disk_path.c_str(),
-                        hipGetErrorString(he));
-                e->disk_path.clear();
-                e->co.clear();
-                e->state = 0;
-                retry = true;
-            }
-        }
-        if (m->mod) {
-            (void)hipModuleUnload(m->mod);
-            m->mod = nullptr;
-        }
-        (void)hipGetLastError();
-        if (retry) {
-            wait = true;                                           // the caller gets the rebuilt kernel, not a second failure
-            continue;
-        }
-        m->failed = true;
-        m->error = std::string("hipModuleLoadData/GetFunction: ") + hipGetErrorString(he);
-        *err = m->error;
-        return m;
-    }
-    m->failed = false;
-    m->loaded = true;
-    return m;
-}
-
-// make sure code / params / tables of `p` are resident on the current device
-static int ensure_resident(sdfk_program* p, int device, hipStream_t stream, DevState** out) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    DevState& d = p->dev[device];
-    if (!d.d_code) {
-        HIPCHK(hipMalloc(&d.d_code, p->code.size() * sizeof(uint32_t)));
-        HIPCHK(hipMemcpy(d.d_code, p->code.data(), p->code.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&d.d_params, std::max<size_t>(p->params.size(), 1) * sizeof(float)));
-        HIPCHK(hipMalloc(&d.d_tables, std::max<size_t>(p->tables.size(), 1) * sizeof(float)));
-        if (!p->tables.empty())
-            HIPCHK(hipMemcpy(d.d_tables, p->tables.data(), p->tables.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (d.params_version != p->params_version) {
-        // enqueued on the caller's stream (it must not overtake kernels of that stream that still read the old values)
-        // and WAITED for: other streams of the device (the two slots of the host pipeline) launch right after this
-        if (!p->params.empty()) {
-            HIPCHK(hipMemcpyAsync(d.d_params, p->params.data(), p->params.size() * sizeof(float),
-                                  hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
-        d.params_version = p->params_version;
-    }
-    *out = &d;
-    return 0;
-}
-
-static inline unsigned blocks_for(long long n, int vec) {
-    return (unsigned)((n + (long long)SDFK_BLOCK * vec - 1) / ((long long)SDFK_BLOCK * vec));
-}
-
-// test aid: statistics of the candidate lists of the last chain-mode launch (sdfk_debug_cells_stats)
-static std::atomic<bool> g_cells_stats_on{false};
-static std::mutex g_cells_stats_mu;
-static long long g_cells_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-extern "C" void sdfk_debug_cells_stats(int enable, long long* out8) {
-    g_cells_stats_on.store(enable != 0);
-    if (out8) {
-        std::lock_guard<std::mutex> lk(g_cells_stats_mu);
-        for (int i = 0; i < 8; ++i) out8[i] = g_cells_stats[i];
-        for (int i = 0; i < 8; ++i) g_cells_stats[i] = 0;
-    }
-}
-// ---- candidate lists of chain-mode programs (sdfk_codegen.cpp: sdfk_cells / sdfk_cellpass / sdfk_spec_cells) ------------------
-struct CellLevelH {           // mirrors sdfk_celllevel
-    unsigned lx, ly, lz, ncx, ncy, ncz, xoff, pad;
-};
-struct CellsArg {             // mirrors sdfk_cells
-    CellLevelH lv;
-    const void *sph, *span, *cand;
-    unsigned enabled, ncells;
-};
-struct CellPassArg {          // mirrors sdfk_cellpass
-    CellLevelH lv, parent;
-    void *sph, *span;
-    const void *psph, *pspan;
-    void* cand;
-    unsigned* head;
-    unsigned base, shard_cap;
-    unsigned ncells, pad0;
-    float inflate, pad;
-};
-static bool parse3(const char* e, unsigned* v) {
-    int a = 0, b = 0, c = 0;
-    if (!e || sscanf(e, "%d,%d,%d", &a, &b, &c) != 3 || a < 0 || b < 0 || c < 0 || a > 12 || b > 12 || c > 12) return false;
-    v[0] = (unsigned)a; v[1] = (unsigned)b; v[2] = (unsigned)c;
-    return true;
-}
-static CellLevelH cell_level(const RowGeom& rg, const unsigned l[3]) {
-    CellLevelH lv{};
-    lv.lx = l[0]; lv.ly = l[1]; lv.lz = l[2];
-    const long long planes = rg.prow ? ((rg.R - rg.seg0) + rg.prow - 1) / rg.prow : 0;
-    lv.xoff = rg.seg0 > 0 ? (1u << lv.lx) : 0u;
-    lv.ncx = planes > 0 ? (unsigned)(((long long)lv.xoff + planes - 1) >> lv.lx) + 1u : 1u;
-    lv.ncy = ((std::max(rg.bpp, rg.nb0) - 1u) >> lv.ly) + 1u;
-    lv.ncz = ((rg.nchunk - 1u) >> lv.lz) + 1u;
-    return lv;
-}
-// Lists for this launch: sizes the levels, (re)allocates the stream's scratch, enqueues the pre-pass (coarse level, then
-// fine) on `stream` and fills what the row-block kernel is handed. cells_fn: sdfk_spec_cells / sdfk_spec_cellsg of the
-// module, `src`: its first kernel arguments after PRM / TAB (array: co, stride; grid: the SrcGrid), n_src of them.
-static int prepare_cells(sdfk_program* p, DevState* d, hipFunction_t cells_fn, const RowGeom& rg, void** src, int n_src,
-                         const float* prm, const float* tab, hipStream_t stream, CellsArg* out) {
-    memset(out, 0, sizeof *out);
-    static const int min_members = [] { const char* e = getenv("SDFK_CELLS_MIN"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 17; }();
-    static const bool off = [] { const char* e = getenv("SDFK_CELLS"); return e && e[0] == '0'; }();
-    if (!cells_fn || off || p->chain_members < min_members) return 0;
-    const bool is3d = rg.prow < (unsigned long long)rg.R;
-    unsigned lf[3] = {is3d ? 3u : 0u, is3d ? 1u : 2u, is3d ? 0u : 1u};            // 8 planes x 32 rows x 32 points | 64 rows x 64 points
-    unsigned lc[3] = {lf[0] + (is3d ? 2u : 0u), lf[1] + 2u, lf[2] + 2u};          // 4 x 4 x 4 (4 x 4) fine cells
-    static const char* e_fine = getenv("SDFK_CELL_FINE");
-    static const char* e_coarse = getenv("SDFK_CELL_COARSE");
-    (void)parse3(e_fine, lf);
-    bool coarse = p->chain_members >= 128;
-    if (e_coarse) coarse = parse3(e_coarse, lc);
-    if (coarse && (lc[0] < lf[0] || lc[1] < lf[1] || lc[2] < lf[2])) coarse = false;
-    const CellLevelH fine = cell_level(rg, lf);
-    const CellLevelH crs = coarse ? cell_level(rg, lc) : CellLevelH{};
-    const unsigned long long nf = (unsigned long long)fine.ncx * fine.ncy * fine.ncz;
-    const unsigned long long nc = coarse ? (unsigned long long)crs.ncx * crs.ncy * crs.ncz : 0ull;
-    if (nf == 0 || nf > 0x3fffffffull || nc > 0x3fffffffull) return 0;
-    // pool: room for 48 entries per fine cell and 1024 per coarse cell (measured lists: a handful / a few hundred); a cell
-    // that finds the pool full makes its bricks probe every member — slower, never wrong
-    // Pool of list entries, per level 256 shards with an allocation head each (sdfk_cells_kernel). The coarse level can
-    // never run out — a shard holds every member for each of its cells —; the fine level gets 256 entries per cell plus
-    // slack (measured lists: a handful to a few dozen entries, a few hundred in scenes where thousands of members overlap).
-    const unsigned long long members = (unsigned long long)p->chain_members, shards = 256;
-    unsigned long long cshard = ((nc + shards - 1) / shards) * members;
-    // (a fine shard serves ceil(cells / 256) cells: every member for each of them, or the budget — but never less than one
-    //  whole list)
-    unsigned long long fshard = std::max(members, std::min(((nf + shards - 1) / shards) * members, (256ull * nf + (16ull << 20) + shards - 1) / shards));
-    if (const char* e = getenv("SDFK_CELLS_POOL")) {             // (tests: a pool too small for the lists)
-        const long long v = atoll(e);
-        if (v > 0) fshard = std::min<unsigned long long>(fshard, (unsigned long long)v);
-    }
-    if (shards * (cshard + fshard) > 0x3fffffffull) return 0;   // (no lists: still correct)
-    const unsigned long long cap = shards * (cshard + fshard);
-    const size_t o_fsph = 0, o_fspan = o_fsph + 16 * nf, o_csph = o_fspan + 8 * nf, o_cspan = o_csph + 16 * nc,
-                 o_head = (o_cspan + 8 * nc + 63) & ~(size_t)63, o_pool = o_head + 2 * 64 * shards, total = o_pool + 4 * cap + 64;
-    CellScratch* cs;
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        cs = &d->cells[stream];
-    }
-    if (cs->bytes < total) {
-        if (cs->buf) {
-            HIPCHK(hipStreamSynchronize(stream));              // (the stream's earlier launches read the old buffer)
-            (void)hipFree(cs->buf);
-            cs->buf = nullptr;
-            cs->bytes = 0;
-        }
-        if (hipMalloc(&cs->buf, total + total / 4) != hipSuccess) { (void)hipGetLastError(); return 0; }   // (no lists: still correct)
-        cs->bytes = total + total / 4;
-    }
-    char* b = cs->buf;
-    HIPCHK(hipMemsetAsync(b + o_head, 0, 2 * 64 * shards, stream));
-    CellPassArg cp{};
-    cp.cand = b + o_pool;
-    if (coarse) {
-        // a coarse cell answers for 1.3 x its circumsphere: room for the circumspheres of the fine cells inside it
-        cp.lv = crs; cp.parent = CellLevelH{}; cp.sph = b + o_csph; cp.span = b + o_cspan; cp.psph = nullptr; cp.pspan = nullptr;
-        cp.ncells = (unsigned)nc; cp.inflate = 1.3f;
-        cp.head = reinterpret_cast<unsigned*>(b + o_head);
-        cp.base = 0u; cp.shard_cap = (unsigned)cshard;
-        std::vector<void*> args = {(void*)&prm, (void*)&tab};
-        for (int i = 0; i < n_src; ++i) args.push_back(src[i]);
-        RowGeom g2 = rg;
-        args.push_back(&g2);
-        args.push_back(&cp);
-        HIPCHK(hipModuleLaunchKernel(cells_fn, (unsigned)((nc + 3) / 4), 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr));
-    }
-    cp.lv = fine; cp.parent = coarse ? crs : CellLevelH{}; cp.sph = b + o_fsph; cp.span = b + o_fspan;
-    cp.psph = coarse ? b + o_csph : nullptr; cp.pspan = coarse ? b + o_cspan : nullptr;
-    cp.ncells = (unsigned)nf; cp.inflate = 1.0f;
-    cp.head = reinterpret_cast<unsigned*>(b + o_head + 64 * shards);
-    cp.base = (unsigned)(shards * cshard); cp.shard_cap = (unsigned)fshard;
-    {
-        std::vector<void*> args = {(void*)&prm, (void*)&tab};
-        for (int i = 0; i < n_src; ++i) args.push_back(src[i]);
-        RowGeom g2 = rg;
-        args.push_back(&g2);
-        args.push_back(&cp);
-        HIPCHK(hipModuleLaunchKernel(cells_fn, (unsigned)((nf + 3) / 4), 1, 1, 256, 1, 1, 0, stream, args.data(), nullptr));
-    }
-    static const bool trace = [] { const char* e = getenv("SDFK_CELLS_TRACE"); return e && e[0] == '1'; }();
-    if (trace || g_cells_stats_on.load()) {                      // (debug: synchronises and reads the lists' statistics back)
-        HIPCHK(hipStreamSynchronize(stream));
-        std::vector<uint2> sp(nf);
-        unsigned head = 0;
-        HIPCHK(hipMemcpy(sp.data(), b + o_fspan, 8 * nf, hipMemcpyDeviceToHost));
-        {
-            std::vector<unsigned> heads(2 * 16 * shards);
-            HIPCHK(hipMemcpy(heads.data(), b + o_head, 2 * 64 * shards, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < heads.size(); i += 16) head += heads[i];
-        }
-        unsigned long long sum = 0, all = 0, empty = 0, mx = 0;
-        for (const uint2& x : sp) {
-            if (x.y == 0xffffffffu) ++all;
-            else { sum += x.y; mx = std::max<unsigned long long>(mx, x.y); if (x.y == 0) ++empty; }
-        }
-        {
-            std::lock_guard<std::mutex> lk(g_cells_stats_mu);
-            g_cells_stats[0] = (long long)nf; g_cells_stats[1] = (long long)nc; g_cells_stats[2] = (long long)head;
-            g_cells_stats[3] = (long long)cap; g_cells_stats[4] = (long long)sum; g_cells_stats[5] = (long long)mx;
-            g_cells_stats[6] = (long long)all; g_cells_stats[7] = (long long)empty;
-        }
-        if (trace) fprintf(stderr, "[sdfk cells] %d members: fine %ux%ux%u = %llu cells (2^%u planes x 2^%u blocks x 2^%u windows), coarse %llu; pool %u of %llu entries; "
-                "fine lists: mean %.1f max %llu, %llu without a list, %llu empty\n", p->chain_members, fine.ncx, fine.ncy, fine.ncz, nf, fine.lx, fine.ly, fine.lz, nc,
-                head, cap, (double)sum / (double)std::max<unsigned long long>(1, nf - all - empty), mx, all, empty);
-    }
-    out->lv = fine;
-    out->sph = b + o_fsph;
-    out->span = b + o_fspan;
-    out->cand = b + o_pool;
-    out->enabled = 1u;
-    out->ncells = (unsigned)nf;
-    return 0;
-}
-
-// flat: the caller states that the rows of the array are rows of a flat grid (z = 0, rows along y); grids know it
-static int run(sdfk_program* p, const SrcArray* arr, const SrcGrid* grid, long long n, float* d_out, void* stream_,
-               int mode, bool vec_ok, long long row_len = 0, const float* aux = nullptr, long long aux_stride = 0,
-               bool flat = false, long long plane_rows = 0, long long plane_phase = 0, unsigned* d_flags = nullptr,
-               unsigned thr_key = 0, bool xy = false) {
-    if (!p) return fail(-1, "null program");
-    if (n < 0) return fail(-1, "negative point count");
-    if (p->n_aux > 0 && (!aux || aux_stride < n))
-        return fail(-1, "this program reads auxiliary fields (staged evaluation): use sdfk_eval_device_aux / sdfk_eval_grid_aux");
-    if (n == 0) return 0;
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    // flags instead of the field (fused selection): the specialised plain / row-block kernels only — the call waits for
-    // their build instead of starting on the interpreter kernel
-    if (d_flags && (mode == SDFK_MODE_AUTO || mode == SDFK_MODE_INTERPRET)) mode = SDFK_MODE_SPECIALIZED;
-    // two-row coordinates (z = 0 by contract): builds of the plain and the flat row-block array kernels that never touch a
-    // third row; the interpreter kernel has no such build, so these calls wait for the specialised kernel too
-    if (xy) {
-        if (!arr || p->n_aux > 0) return fail(-1, "two-row coordinates: array source, no auxiliary fields");
-        if (mode == SDFK_MODE_AUTO || mode == SDFK_MODE_INTERPRET) mode = SDFK_MODE_SPECIALIZED;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, stream, &d);
-    if (rc) return rc;
-
-    // split into a 4-wide body and a scalar tail
-    long long n4 = vec_ok ? (n / 4) * 4 : 0;
-    long long tail = n - n4;
-
-    // Build time bounds (programs that are not chains: those are table-driven and build in under a second whatever their
-    // size). hiprtc's time grows faster than the program — profiles/r04_build_time.txt, left-deep smooth-union chains on
-    // the build container's CPU: row blocks 1 / 4 / 8 / 21 / 102 s at 29 / 89 / 179 / 299 / 449 instructions with the full
-    // pipeline; beyond SDFK_BIG_PROGRAM (300) instructions builds run without CodeGenPrepare and VectorCombine
-    // (rtc_options): row blocks 21 / 30 / 49 / 85 s at 449 / 599 / 899 / 1199, line bricks 8 / 11 / 22 / 33 s, the plain
-    // kernel 4 / 6 / 12 / 25 s (on the GPU boxes' CPUs less than half of that). With skip bits for 512 sites a row-block
-    // kernel is 2-3 x a line-brick one on these programs, so both limits are the same now:
-    //   row blocks up to SDFK_ROWS_LIMIT instructions (1200), line bricks (or, for unaligned arrays, the plain kernel) up to
-    //   SDFK_SPECIALIZE_LIMIT (1200); beyond that AUTO stays on the interpreter kernel, which needs no compilation.
-    // A background build that is still running when the process leaves is killed (sdfk_jit_cancel).
-    // MODE_SPECIALIZED / NOCULL always build (the caller asked for the kernel and waits), with the same choice of flavour.
-    static const long long spec_limit = [] {
-        const char* e = getenv("SDFK_SPECIALIZE_LIMIT");
-        const long long v = e ? atoll(e) : 1200;
-        return v > 0 ? v : 1200;
-    }();
-    static const long long rows_limit = [] {
-        const char* e = getenv("SDFK_ROWS_LIMIT");
-        const long long v = e ? atoll(e) : 1200;
-        return v > 0 ? v : 1200;
-    }();
-    if (mode == SDFK_MODE_AUTO && (long long)(p->code.size() / 2) > spec_limit && p->interp_ok && !p->chain_mode && !d_flags)
-        mode = SDFK_MODE_INTERPRET;
-
-    // Which flavour does this call launch? (row blocks > line bricks > plain; NOCULL and programs without sites: plain)
-    RowGeom rg;
-    int flavour = arr ? SDFK_FL_PLAIN_ARRAY : SDFK_FL_PLAIN_GRID;
-    const long long grow = grid ? (grid->n2 > 1 ? (long long)grid->n2 : (long long)grid->n1) : 0;
-    if (!p->sites.empty() && mode != SDFK_MODE_NOCULL && mode != SDFK_MODE_INTERPRET) {
-        // (chain mode: row blocks of ONE plane each — the cells of its candidate lists are boxes of the grid)
-        if (arr && rows_geometry(n, row_len, &rg, (flat || d_flags) ? 0 : plane_rows, plane_phase, p->chain_mode))
-            flavour = (flat || xy) ? SDFK_FL_ROWS2D_ARRAY : SDFK_FL_ROWS_ARRAY;   // rows need no alignment beyond 4 bytes
-        else if (arr && vec_ok && !p->chain_mode && !d_flags && !xy) flavour = SDFK_FL_TILE_ARRAY;
-        else if (grid && grid->start % grow == 0 &&
-                 rows_geometry(n, grow, &rg, (grid->n2 > 1 && !d_flags) ? (long long)grid->n1 : 0,    // (flags: the slot layout
-                               grid->n2 > 1 ? (grid->start / grow) % (long long)grid->n1 : 0, p->chain_mode))   //  knows blocks of 16 rows)
-            flavour = grid->n2 > 1 ? SDFK_FL_ROWS_GRID : SDFK_FL_ROWS2D_GRID;
-        else if (grid && vec_ok && !p->chain_mode && !d_flags) flavour = SDFK_FL_TILE_GRID;
-        // (too big for a row-block build within the budget: the line-brick kernel where the call allows it, else un-culled)
-        if (!p->chain_mode && (long long)(p->code.size() / 2) > rows_limit &&
-            (flavour == SDFK_FL_ROWS_ARRAY || flavour == SDFK_FL_ROWS2D_ARRAY || flavour == SDFK_FL_ROWS_GRID || flavour == SDFK_FL_ROWS2D_GRID)) {
-            const bool is_arr = arr != nullptr;
-            if (vec_ok && !d_flags && !xy) flavour = is_arr ? SDFK_FL_TILE_ARRAY : SDFK_FL_TILE_GRID;
-            else if (!d_flags) flavour = is_arr ? SDFK_FL_PLAIN_ARRAY : SDFK_FL_PLAIN_GRID;
-        }
-    }
-    std::shared_ptr<SpecModule> sk;
-    if (mode != SDFK_MODE_INTERPRET) {
-        // AUTO: while hiprtc is still building this flavour (background thread, SDFK_ASYNC_JIT=0 turns that off) the
-        // call is served by the interpreter kernel — the same device functions, the same bits — and later calls
-        // switch over. SPECIALIZED / NOCULL always wait for the build.
-        static const bool async_jit = [] { const char* e = getenv("SDFK_ASYNC_JIT"); return !(e && e[0] == '0'); }();
-        const bool wait = mode != SDFK_MODE_AUTO || !p->interp_ok || !async_jit;
-        std::string err;
-        sk = get_module(p, device, flavour, wait, &err, (d_flags ? 1 : 0) | (xy ? 2 : 0));
-        if (sk && sk->failed) {
-            if (mode == SDFK_MODE_SPECIALIZED || !p->interp_ok)
-                return fail(-3, "specialised kernel unavailable: " + err);
-            static bool warned = false;
-            if (!warned) {
-                fprintf(stderr, "[sdfk] hiprtc specialisation failed, using the interpreter kernel: %s\n", err.c_str());
-                warned = true;
-            }
-            sk.reset();
-        }
-    }
-    if (!sk && !p->interp_ok)
-        return fail(-4, "program needs more registers than the interpreter kernel has (use the specialised mode)");
-
-    const float* prm = d->d_params;
-    const float* tab = d->d_tables;
-    if (sk) {
-        if (flavour == SDFK_FL_ROWS_ARRAY || flavour == SDFK_FL_ROWS_GRID || flavour == SDFK_FL_ROWS2D_ARRAY ||
-            flavour == SDFK_FL_ROWS2D_GRID) {
-            const unsigned per_tile = (unsigned)(rows_waves(p) * rows_wbricks(p));
-            const unsigned tiles = ((rg.nbricks + per_tile - 1) / per_tile + 127u) & ~127u;   // whole rounds of 8 XCDs x SDFK_XGROUP = 16 tiles (sdfk_codegen.cpp)
-            const unsigned rthreads = 64u * (unsigned)rows_waves(p);
-            // (chain-mode builds take one more argument, their candidate lists: prepare_cells; fn[1] = the pre-pass kernel)
-            CellsArg cells{};
-            const bool with_cells = p->chain_mode && sk->fn[1] != nullptr;
-            if (arr) {
-                const float* co = arr->co;
-                long long stride = arr->stride;
-                if (with_cells) {
-                    void* src[] = {&co, &stride};
-                    rc = prepare_cells(p, d, sk->fn[1], rg, src, 2, prm, tab, stream, &cells);
-                    if (rc) return rc;
-                }
-                void* args[] = {&prm, &tab, &co, &stride, &rg, &d_out, &d_flags, &thr_key, &cells};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], tiles, 1, 1, rthreads, 1, 1, 0, stream, args, nullptr));
-            } else {
-                // whole grid rows (x-slabs of a sharded evaluation always are); rows along the third axis, or along
-                // the second one when the grid is flat (n2 == 1)
-                SrcGrid g = *grid;
-                rg.row0 = grid->start / grow;
-                rg.yrows = grid->n2 > 1 ? 0 : 1;
-                if (with_cells) {
-                    void* src[] = {&g};
-                    rc = prepare_cells(p, d, sk->fn[1], rg, src, 1, prm, tab, stream, &cells);
-                    if (rc) return rc;
-                }
-                void* args[] = {&prm, &tab, &g, &rg, &d_out, &d_flags, &thr_key, &cells};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], tiles, 1, 1, rthreads, 1, 1, 0, stream, args, nullptr));
-            }
-            return 0;
-        }
-        if (flavour == SDFK_FL_TILE_ARRAY || flavour == SDFK_FL_TILE_GRID) {
-            // brick-culling tile kernel: handles the ragged end itself
-            const unsigned tiles = (unsigned)((n + tile_points() - 1) / tile_points());
-            if (arr) {
-                const float* co = arr->co;
-                long long stride = arr->stride;
-                void* args[] = {&prm, &tab, &co, &stride, &n, &d_out};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], tiles, 1, 1, tile_threads(), 1, 1, 0, stream, args, nullptr));
-            } else {
-                SrcGrid g = *grid;
-                void* args[] = {&prm, &tab, &g, &n, &d_out};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], tiles, 1, 1, tile_threads(), 1, 1, 0, stream, args, nullptr));
-            }
-            return 0;
-        }
-        if (arr) {
-            const float* co = arr->co;
-            long long stride = arr->stride;
-            if (n4) {
-                long long off = 0;
-                void* args[] = {&prm, &tab, &co, &stride, &off, &n4, &d_out, &aux, &aux_stride, &d_flags, &thr_key};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], blocks_for(n4, 4), 1, 1, SDFK_BLOCK, 1, 1, 0, stream, args,
-                                             nullptr));
-            }
-            if (tail) {
-                long long off = n4;
-                void* args[] = {&prm, &tab, &co, &stride, &off, &tail, &d_out, &aux, &aux_stride, &d_flags, &thr_key};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[1], blocks_for(tail, 1), 1, 1, SDFK_BLOCK, 1, 1, 0, stream, args,
-                                             nullptr));
-            }
-        } else {
-            SrcGrid g = *grid;
-            if (n4) {
-                long long off = 0;
-                void* args[] = {&prm, &tab, &g, &off, &n4, &d_out, &aux, &aux_stride, &d_flags, &thr_key};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[0], blocks_for(n4, 4), 1, 1, SDFK_BLOCK, 1, 1, 0, stream, args,
-                                             nullptr));
-            }
-            if (tail) {
-                long long off = n4;
-                void* args[] = {&prm, &tab, &g, &off, &tail, &d_out, &aux, &aux_stride, &d_flags, &thr_key};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[1], blocks_for(tail, 1), 1, 1, SDFK_BLOCK, 1, 1, 0, stream, args,
-                                             nullptr));
-            }
-        }
-        return 0;
-    }
-    // interpreter
-    if (d_flags) return fail(-3, "fused selection needs the specialised kernels");
-    const int n_instr = (int)(p->code.size() / 2);
-    const long long zero = 0;
-    auto launch = [&](auto src, int vec, long long off, long long cnt) {
-        using SRC = decltype(src);
-        const dim3 grid(blocks_for(cnt, vec)), block(SDFK_BLOCK);
-#define SDFK_INTERP_GO(VEC, NC, NV) hipLaunchKernelGGL((sdfk_interp_kernel<VEC, NC, NV, SRC>), grid, block, 0, stream, d->d_code, \
-                                                        n_instr, prm, tab, src, off, cnt, d_out, p->result_reg, aux, aux_stride)
-        if (vec == 4) {
-            if (p->interp_small) SDFK_INTERP_GO(4, SDFK_NC_SMALL, SDFK_NV_SMALL);
-            else SDFK_INTERP_GO(4, SDFK_NC, SDFK_NV);
-        } else {
-            if (p->interp_small) SDFK_INTERP_GO(1, SDFK_NC_SMALL, SDFK_NV_SMALL);
-            else SDFK_INTERP_GO(1, SDFK_NC, SDFK_NV);
-        }
-#undef SDFK_INTERP_GO
-    };
-    if (arr) {
-        if (n4) launch(*arr, 4, zero, n4);
-        if (tail) launch(*arr, 1, n4, tail);
-    } else {
-        if (n4) launch(*grid, 4, zero, n4);
-        if (tail) launch(*grid, 1, n4, tail);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// What the array entry points check before anything runs, and the request they hand to run(): device pointers, the row
+// stride, the row length (min_row_len 1: the call has one; 0: it may pass none; -1: the call has no such argument), and
+// whether rows and output allow 16-byte accesses.
+static int array_entry(const char* who, sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
+                       int min_row_len, float* d_out, void* stream, int mode, SrcArray* a, EvalCall* c) {
+    if (!d_co || !d_out) return fail(-1, std::string(who) + ": null device pointer");
+    if (row_stride < n) return fail(-1, std::string(who) + ": row stride smaller than the point count");
+    if (min_row_len >= 0 && (row_len < min_row_len || (row_len > 0 && n > 0 && n % row_len != 0)))
+        return fail(-1, std::string(who) + ": the point count is not a multiple of the row length");
+    *a = {d_co, (long long)row_stride};
+    *c = array_call(p, a, n, d_out, stream, mode, aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0));
+    c->row_len = min_row_len >= 0 ? row_len : 0;
+    return 0;
+}
+
 extern "C" int sdfk_eval_device(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, float* d_out,
                                 void* stream, int mode) {
-    if (!d_co || !d_out) return fail(-1, "sdfk_eval_device: null device pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device: row stride smaller than the point count");
-    SrcArray a = {d_co, (long long)row_stride};
-    bool vec_ok = aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok);
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device", p, d_co, n, row_stride, 0, -1, d_out, stream, mode, &a, &c);
+    return rc ? rc : run(c);
 }
 
 extern "C" int sdfk_eval_device_rows(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
                                      float* d_out, void* stream, int mode) {
-    if (!d_co || !d_out) return fail(-1, "sdfk_eval_device_rows: null device pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device_rows: row stride smaller than the point count");
-    if (row_len < 1 || (n > 0 && n % row_len != 0))
-        return fail(-1, "sdfk_eval_device_rows: the point count is not a multiple of the row length");
-    SrcArray a = {d_co, (long long)row_stride};
-    bool vec_ok = aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok, row_len);
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device_rows", p, d_co, n, row_stride, row_len, 1, d_out, stream, mode, &a, &c);
+    return rc ? rc : run(c);
 }
 
 /* include/sdfk.h: two coordinate rows, z = 0 by contract */
 extern "C" int sdfk_eval_device_rows2d_xy(sdfk_program* p, const float* d_xy, int64_t n, int64_t row_stride, int64_t row_len,
                                           float* d_out, void* stream, int mode) {
-    if (!d_xy || !d_out) return fail(-1, "sdfk_eval_device_rows2d_xy: null device pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device_rows2d_xy: row stride smaller than the point count");
-    if (row_len < 0 || (row_len > 0 && n > 0 && n % row_len != 0))
-        return fail(-1, "sdfk_eval_device_rows2d_xy: the point count is not a multiple of the row length");
-    SrcArray a = {d_xy, (long long)row_stride};
-    bool vec_ok = aligned16(d_xy) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok, row_len, nullptr, 0, row_len > 0, 0, 0, nullptr, 0, true);
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device_rows2d_xy", p, d_xy, n, row_stride, row_len, 0, d_out, stream, mode, &a, &c);
+    if (rc) return rc;
+    c.flat = row_len > 0;
+    c.xy = true;
+    return run(c);
 }
 
 extern "C" int sdfk_eval_device_rows3d(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
                                        int64_t plane_rows, int64_t first_row_in_plane, float* d_out, void* stream, int mode) {
-    if (!d_co || !d_out) return fail(-1, "sdfk_eval_device_rows3d: null device pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device_rows3d: row stride smaller than the point count");
-    if (row_len < 1 || (n > 0 && n % row_len != 0))
-        return fail(-1, "sdfk_eval_device_rows3d: the point count is not a multiple of the row length");
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device_rows3d", p, d_co, n, row_stride, row_len, 1, d_out, stream, mode, &a, &c);
+    if (rc) return rc;
     if (plane_rows < 0 || first_row_in_plane < 0 || (plane_rows > 0 && first_row_in_plane >= plane_rows))
         return fail(-1, "sdfk_eval_device_rows3d: plane_rows >= 0 and 0 <= first_row_in_plane < plane_rows");
-    SrcArray a = {d_co, (long long)row_stride};
-    bool vec_ok = aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok, row_len, nullptr, 0, false, plane_rows, first_row_in_plane);
+    c.plane_rows = plane_rows;
+    c.plane_phase = first_row_in_plane;
+    return run(c);
 }
 
 extern "C" int sdfk_eval_device_rows2d(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
                                        float* d_out, void* stream, int mode) {
-    if (!d_co || !d_out) return fail(-1, "sdfk_eval_device_rows2d: null device pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device_rows2d: row stride smaller than the point count");
-    if (row_len < 1 || (n > 0 && n % row_len != 0))
-        return fail(-1, "sdfk_eval_device_rows2d: the point count is not a multiple of the row length");
-    SrcArray a = {d_co, (long long)row_stride};
-    bool vec_ok = aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok, row_len, nullptr, 0, true);
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device_rows2d", p, d_co, n, row_stride, row_len, 1, d_out, stream, mode, &a, &c);
+    if (rc) return rc;
+    c.flat = true;
+    return run(c);
 }
 
 extern "C" int sdfk_eval_device_aux(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, const float* d_aux,
                                     int n_aux, int64_t aux_stride, float* d_out, void* stream, int mode) {
-    if (!p || !d_co || !d_out) return fail(-1, "sdfk_eval_device_aux: null pointer");
-    if (row_stride < n) return fail(-1, "sdfk_eval_device_aux: row stride smaller than the point count");
+    if (!p) return fail(-1, "sdfk_eval_device_aux: null pointer");
+    SrcArray a;
+    EvalCall c;
+    const int rc = array_entry("sdfk_eval_device_aux", p, d_co, n, row_stride, 0, -1, d_out, stream, mode, &a, &c);
+    if (rc) return rc;
     if (n_aux < p->n_aux) return fail(-1, "sdfk_eval_device_aux: the program reads more auxiliary fields than were passed");
-    SrcArray a = {d_co, (long long)row_stride};
-    bool vec_ok = aligned16(d_co) && aligned16(d_out) && (row_stride % 4 == 0);
-    return run(p, &a, nullptr, n, d_out, stream, mode, vec_ok, 0, d_aux, aux_stride);
+    c.aux = d_aux;
+    c.aux_stride = aux_stride;
+    return run(c);
+}
+
+/* include/sdfk.h: the plan of a request, no device touched */
+extern "C" int sdfk_debug_eval_plan(sdfk_program* p, const int64_t* request, int64_t* plan) {
+    if (!p || !request || !plan) return fail(-1, "sdfk_debug_eval_plan: null argument");
+    if (request[1] <= 0) return fail(-1, "sdfk_debug_eval_plan: the point count must be positive");
+    if (request[0] && (request[10] < 1 || request[11] < 1 || request[12] < 0))
+        return fail(-1, "sdfk_debug_eval_plan: grid sizes from 1, start from 0");
+    SrcArray a = {nullptr, 0};
+    SrcGrid g = {nullptr, nullptr, nullptr, (unsigned)request[10], (unsigned)request[11], (long long)request[12]};
+    unsigned some_flags = 0;                                    // (the planner asks whether flags are written, not where)
+    EvalCall c = request[0] ? grid_call(p, &g, request[1], nullptr, nullptr, (int)request[2], request[3] != 0)
+                            : array_call(p, &a, request[1], nullptr, nullptr, (int)request[2], request[3] != 0);
+    c.row_len = request[4];
+    c.flat = request[5] != 0;
+    c.plane_rows = request[6];
+    c.plane_phase = request[7];
+    if (request[8]) c.d_flags = &some_flags;
+    c.xy = request[9] != 0;
+    EvalPlan pl;
+    const int rc = plan_eval(c, plan_env(), &pl);
+    if (rc) return rc;
+    plan[0] = pl.mode;
+    plan[1] = pl.flavour;
+    plan[2] = pl.needs_specialised ? 1 : 0;
+    plan[3] = pl.rows() ? (int64_t)pl.rg.nbricks : 0;
+    return 0;
 }
 
 extern "C" int sdfk_debug_row_masks(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
@@ -1875,21 +704,16 @@ extern "C" int sdfk_debug_row_masks(sdfk_program* p, const float* d_co, int64_t 
     if (n_bricks) *n_bricks = rg.nbricks;
     if (brick_rows) *brick_rows = 16;
     if (!d_masks) return 0;                      // size query
-    hipStream_t stream = (hipStream_t)stream_;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, stream, &d);
+    LaunchCtx x;
+    int rc = launch_ctx(p, stream_, &x);
     if (rc) return rc;
-    std::string err;
-    std::shared_ptr<SpecModule> sk = get_module(p, device, SDFK_FL_ROWS_MASK, true, &err);
-    if (!sk || sk->failed) return fail(-3, "specialised kernel unavailable: " + err);
-    const float* prm = d->d_params;
-    const float* tab = d->d_tables;
+    std::shared_ptr<SpecModule> sk;
+    rc = pick_kernel(p, x.device, SDFK_FL_ROWS_MASK, 0, SDFK_MODE_SPECIALIZED, false, "kernel", false, &sk);
+    if (rc) return rc;
     long long stride = row_stride;
-    void* args[] = {&prm, &tab, &d_co, &stride, &rg, &d_masks};
+    void* args[] = {&x.prm, &x.tab, &d_co, &stride, &rg, &d_masks};
     const unsigned per_tile = (unsigned)(rows_waves(p) * rows_wbricks(p));
-    HIPCHK(hipModuleLaunchKernel(sk->fn[0], (rg.nbricks + per_tile - 1) / per_tile, 1, 1, 64 * rows_waves(p), 1, 1, 0, stream,
+    HIPCHK(hipModuleLaunchKernel(sk->fn[0], (rg.nbricks + per_tile - 1) / per_tile, 1, 1, 64 * rows_waves(p), 1, 1, 0, x.stream,
                                  args, nullptr));
     return 0;
 }
@@ -1901,21 +725,16 @@ extern "C" int sdfk_debug_brick_masks(sdfk_program* p, const float* d_co, int64_
         return fail(-1, "sdfk_debug_brick_masks: needs 16-byte aligned rows");
     if (p->sites.empty()) return fail(-2, "sdfk_debug_brick_masks: program has no cull sites");
     if (p->chain_mode) return fail(-2, "sdfk_debug_brick_masks: chain-mode programs have no line-brick flavour");
-    hipStream_t stream = (hipStream_t)stream_;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, stream, &d);
+    LaunchCtx x;
+    int rc = launch_ctx(p, stream_, &x);
     if (rc) return rc;
-    std::string err;
-    std::shared_ptr<SpecModule> sk = get_module(p, device, SDFK_FL_TILE_MASK, true, &err);
-    if (!sk || sk->failed) return fail(-3, "specialised kernel unavailable: " + err);
-    const float* prm = d->d_params;
-    const float* tab = d->d_tables;
+    std::shared_ptr<SpecModule> sk;
+    rc = pick_kernel(p, x.device, SDFK_FL_TILE_MASK, 0, SDFK_MODE_SPECIALIZED, false, "kernel", false, &sk);
+    if (rc) return rc;
     long long stride = row_stride, nn = n;
-    void* args[] = {&prm, &tab, &d_co, &stride, &nn, &d_masks};
+    void* args[] = {&x.prm, &x.tab, &d_co, &stride, &nn, &d_masks};
     HIPCHK(hipModuleLaunchKernel(sk->fn[0], (unsigned)((n + tile_points() - 1) / tile_points()), 1, 1, tile_threads(),
-                                 1, 1, 0, stream, args, nullptr));
+                                 1, 1, 0, x.stream, args, nullptr));
     return 0;
 }
 
@@ -1963,21 +782,6 @@ static int upload_axes(const float* ax0, int64_t n0, const float* ax1, int64_t n
     return 0;
 }
 
-extern "C" int sdfk_eval_grid(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
-                              const float* ax2, int64_t n2, int64_t start, int64_t count, float* d_out, void* stream,
-                              int mode) {
-    if (!d_out) return fail(-1, "sdfk_eval_grid: null output");
-    if (start < 0 || count < 0 || start + count > n0 * n1 * n2) return fail(-1, "sdfk_eval_grid: range outside the grid");
-    AxisTables t;
-    SrcGrid g;
-    int rc = upload_axes(ax0, n0, ax1, n1, ax2, n2, (hipStream_t)stream, &t, &g, start);
-    if (rc) return rc;
-    rc = run(p, nullptr, &g, count, d_out, stream, mode, aligned16(d_out));
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // the axis tables are freed on return
-    return 0;
-}
-
 extern "C" int sdfk_eval_grid_aux(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
                                   const float* ax2, int64_t n2, int64_t start, int64_t count, const float* d_aux, int n_aux,
                                   int64_t aux_stride, float* d_out, void* stream, int mode) {
@@ -1988,10 +792,22 @@ extern "C" int sdfk_eval_grid_aux(sdfk_program* p, const float* ax0, int64_t n0,
     SrcGrid g;
     int rc = upload_axes(ax0, n0, ax1, n1, ax2, n2, (hipStream_t)stream, &t, &g, start);
     if (rc) return rc;
-    rc = run(p, nullptr, &g, count, d_out, stream, mode, aligned16(d_out), 0, d_aux, aux_stride);
+    EvalCall c = grid_call(p, &g, count, d_out, stream, mode, aligned16(d_out));
+    c.aux = d_aux;
+    c.aux_stride = aux_stride;
+    rc = run(c);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // the axis tables are freed on return
     return 0;
+}
+extern "C" int sdfk_eval_grid(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
+                              const float* ax2, int64_t n2, int64_t start, int64_t count, float* d_out, void* stream,
+                              int mode) {
+    if (!d_out) return fail(-1, "sdfk_eval_grid: null output");
+    if (start < 0 || count < 0 || start + count > n0 * n1 * n2) return fail(-1, "sdfk_eval_grid: range outside the grid");
+    if (!p) return fail(-1, "null program");
+    // (no auxiliary fields to pass: a program that reads some is refused by run(), as ever)
+    return sdfk_eval_grid_aux(p, ax0, n0, ax1, n1, ax2, n2, start, count, nullptr, p->n_aux, 0, d_out, stream, mode);
 }
 
 // Host-buffer convenience for grids: evaluate flat indices [start, start+count) of the grid in device chunks
@@ -2015,7 +831,7 @@ extern "C" int sdfk_eval_grid_host(sdfk_program* p, const float* ax0, int64_t n0
     for (int64_t s = 0; s < count && rc == 0; s += chunk) {
         const int64_t m = std::min(chunk, count - s);
         g.start = start + s;
-        rc = run(p, nullptr, &g, m, d_out, nullptr, mode, true);
+        rc = run(grid_call(p, &g, m, d_out, nullptr, mode, true));
         if (rc == 0 && hipMemcpy(out + s, d_out, (size_t)m * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(-6, "sdfk_eval_grid_host: device-to-host copy failed");
     }
@@ -2023,17 +839,20 @@ extern "C" int sdfk_eval_grid_host(sdfk_program* p, const float* ax0, int64_t n0
     return rc;
 }
 
-// One process, several devices: device d evaluates the d-th slab of whole grid rows and copies it into its part of
-// the host field; the slabs run concurrently (one host thread per device). The per-device state of a program and
-// the kernel cache are keyed by device, so this is sdfk_eval_grid_host once per slab.
-extern "C" int sdfk_eval_grid_sharded(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
-                                      const float* ax2, int64_t n2, int n_shards, const int* devices, float* out,
-                                      int mode) {
-    if (!p || !out) return fail(-1, "sdfk_eval_grid_sharded: null argument");
-    if (n_shards < 1 || n_shards > 64) return fail(-1, "sdfk_eval_grid_sharded: 1..64 shards");
+// The partition both sharded calls share: the grid in n_shards slabs of whole rows, shard d on devices[d] (without a
+// list: round-robin over the box), one host thread per shard running body(device, start, count). An error text is
+// thread-local, so the first failing shard's is carried to the caller's thread.
+template <typename Body>
+static int for_each_shard(const char* who, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                          int64_t n2, int n_shards, const int* devices, Body body) {
+    if (n_shards < 1 || n_shards > 64) return fail(-1, std::string(who) + ": 1..64 shards");
     if (!ax0 || !ax1 || !ax2 || n0 < 1 || n1 < 1 || n2 < 1) return fail(-1, "grid axes missing or empty");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return fail(-8, "sdfk_eval_grid_sharded: no HIP device");
+    const int n_dev = sdfk_device_count();
+    if (n_dev < 1) return fail(-8, std::string(who) + ": no HIP device");
+    for (int d = 0; d < n_shards; ++d) {
+        const int dev = devices ? devices[d] : d % n_dev;
+        if (dev < 0 || dev >= n_dev) return fail(-1, std::string(who) + ": device index out of range");
+    }
     const int64_t total = n0 * n1 * n2, unit = n2 > 1 ? n2 : n1;
     const int64_t per = (total / unit / n_shards) * unit;
     std::vector<int> rc((size_t)n_shards, 0);
@@ -2041,20 +860,29 @@ extern "C" int sdfk_eval_grid_sharded(sdfk_program* p, const float* ax0, int64_t
     std::vector<std::thread> workers;
     for (int d = 0; d < n_shards; ++d) {
         const int dev = devices ? devices[d] : d % n_dev;
-        if (dev < 0 || dev >= n_dev) return fail(-1, "sdfk_eval_grid_sharded: device index out of range");
-    }
-    for (int d = 0; d < n_shards; ++d) {
-        const int dev = devices ? devices[d] : d % n_dev;
         const int64_t start = d * per, count = d < n_shards - 1 ? per : total - start;
         workers.emplace_back([=, &rc, &msg] {
-            rc[(size_t)d] = count > 0 ? sdfk_eval_grid_host(p, ax0, n0, ax1, n1, ax2, n2, start, count, out + start, dev, mode) : 0;
-            if (rc[(size_t)d]) msg[(size_t)d] = sdfk_last_error();     // thread-local: carry it to the caller's thread
+            rc[(size_t)d] = count > 0 ? body(dev, start, count) : 0;
+            if (rc[(size_t)d]) msg[(size_t)d] = sdfk_last_error();
         });
     }
     for (std::thread& t : workers) t.join();
     for (int d = 0; d < n_shards; ++d)
         if (rc[(size_t)d]) return fail(rc[(size_t)d], "shard " + std::to_string(d) + ": " + msg[(size_t)d]);
     return 0;
+}
+
+// One process, several devices: device d evaluates the d-th slab of whole grid rows and copies it into its part of
+// the host field; the slabs run concurrently. The per-device state of a program and the kernel cache are keyed by
+// device, so this is sdfk_eval_grid_host once per slab.
+extern "C" int sdfk_eval_grid_sharded(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
+                                      const float* ax2, int64_t n2, int n_shards, const int* devices, float* out,
+                                      int mode) {
+    if (!p || !out) return fail(-1, "sdfk_eval_grid_sharded: null argument");
+    return for_each_shard("sdfk_eval_grid_sharded", ax0, n0, ax1, n1, ax2, n2, n_shards, devices,
+                          [=](int dev, int64_t start, int64_t count) {
+                              return sdfk_eval_grid_host(p, ax0, n0, ax1, n1, ax2, n2, start, count, out + start, dev, mode);
+                          });
 }
 
 // The same partition with the field left ON THE DEVICES: shard d is evaluated on devices[d] and lands in its place of
@@ -2065,53 +893,30 @@ extern "C" int sdfk_eval_grid_sharded_device(sdfk_program* p, const float* ax0, 
                                              const float* ax2, int64_t n2, int n_shards, const int* devices,
                                              int gather_device, float* d_full, int mode) {
     if (!p || !d_full) return fail(-1, "sdfk_eval_grid_sharded_device: null argument");
-    if (n_shards < 1 || n_shards > 64) return fail(-1, "sdfk_eval_grid_sharded_device: 1..64 shards");
-    if (!ax0 || !ax1 || !ax2 || n0 < 1 || n1 < 1 || n2 < 1) return fail(-1, "grid axes missing or empty");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return fail(-8, "sdfk_eval_grid_sharded_device: no HIP device");
-    if (gather_device < 0 || gather_device >= n_dev) return fail(-1, "sdfk_eval_grid_sharded_device: gather device out of range");
-    for (int d = 0; d < n_shards; ++d) {
-        const int dev = devices ? devices[d] : d % n_dev;
-        if (dev < 0 || dev >= n_dev) return fail(-1, "sdfk_eval_grid_sharded_device: device index out of range");
-    }
-    const int64_t total = n0 * n1 * n2, unit = n2 > 1 ? n2 : n1;
-    const int64_t per = (total / unit / n_shards) * unit;
-    std::vector<int> rc((size_t)n_shards, 0);
-    std::vector<std::string> msg((size_t)n_shards);
-    std::vector<std::thread> workers;
-    for (int d = 0; d < n_shards; ++d) {
-        const int dev = devices ? devices[d] : d % n_dev;
-        const int64_t start = d * per, count = d < n_shards - 1 ? per : total - start;
-        workers.emplace_back([=, &rc, &msg] {
-            auto shard = [&]() -> int {
-                if (count <= 0) return 0;
-                HIPCHK(hipSetDevice(dev));
-                hipStream_t stream = nullptr;
-                HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-                // (SDFK_FORCE_PEER_COPY=1: the copy path also for the shards of the gather device — how a one-GPU box tests it)
-                static const bool force_copy = [] { const char* e = getenv("SDFK_FORCE_PEER_COPY"); return e && e[0] == '1'; }();
-                const bool in_place = dev == gather_device && !force_copy;
-                float* d_slab = in_place ? d_full + start : nullptr;
-                int r = 0;
-                if (!d_slab && hipMalloc(&d_slab, (size_t)count * sizeof(float)) != hipSuccess) r = fail(-5, "out of device memory for the slab");
-                if (r == 0) r = sdfk_eval_grid(p, ax0, n0, ax1, n1, ax2, n2, start, count, d_slab, stream, mode);   // (synchronises)
-                if (r == 0 && !in_place) {
-                    if (hipMemcpyPeerAsync(d_full + start, gather_device, d_slab, dev, (size_t)count * sizeof(float), stream) != hipSuccess ||
-                        hipStreamSynchronize(stream) != hipSuccess)
-                        r = fail(-6, "peer copy of the slab failed");
-                }
-                if (!in_place && d_slab) (void)hipFree(d_slab);
-                (void)hipStreamDestroy(stream);
-                return r;
-            };
-            rc[(size_t)d] = shard();
-            if (rc[(size_t)d]) msg[(size_t)d] = sdfk_last_error();
-        });
-    }
-    for (std::thread& t : workers) t.join();
-    for (int d = 0; d < n_shards; ++d)
-        if (rc[(size_t)d]) return fail(rc[(size_t)d], "shard " + std::to_string(d) + ": " + msg[(size_t)d]);
-    return 0;
+    const int n_dev = sdfk_device_count();                      // (none: for_each_shard says so)
+    if (n_dev > 0 && (gather_device < 0 || gather_device >= n_dev))
+        return fail(-1, "sdfk_eval_grid_sharded_device: gather device out of range");
+    return for_each_shard("sdfk_eval_grid_sharded_device", ax0, n0, ax1, n1, ax2, n2, n_shards, devices,
+                          [=](int dev, int64_t start, int64_t count) -> int {
+        HIPCHK(hipSetDevice(dev));
+        hipStream_t stream = nullptr;
+        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        // (SDFK_FORCE_PEER_COPY=1: the copy path also for the shards of the gather device — how a one-GPU box tests it)
+        static const bool force_copy = [] { const char* e = getenv("SDFK_FORCE_PEER_COPY"); return e && e[0] == '1'; }();
+        const bool in_place = dev == gather_device && !force_copy;
+        float* d_slab = in_place ? d_full + start : nullptr;
+        int r = 0;
+        if (!d_slab && hipMalloc(&d_slab, (size_t)count * sizeof(float)) != hipSuccess) r = fail(-5, "out of device memory for the slab");
+        if (r == 0) r = sdfk_eval_grid(p, ax0, n0, ax1, n1, ax2, n2, start, count, d_slab, stream, mode);   // (synchronises)
+        if (r == 0 && !in_place) {
+            if (hipMemcpyPeerAsync(d_full + start, gather_device, d_slab, dev, (size_t)count * sizeof(float), stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess)
+                r = fail(-6, "peer copy of the slab failed");
+        }
+        if (!in_place && d_slab) (void)hipFree(d_slab);
+        (void)hipStreamDestroy(stream);
+        return r;
+    });
 }
 
 extern "C" int sdfk_grid_fill(float* d_co, int64_t row_stride, const float* ax0, int64_t n0, const float* ax1,

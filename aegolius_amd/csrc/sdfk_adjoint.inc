@@ -435,29 +435,22 @@ extern "C" int sdfk_eval_vjp_device(sdfk_program* p, const float* d_co, int64_t 
         if (h_loss) *h_loss = 0.0;
         return 0;
     }
-    hipStream_t s = (hipStream_t)stream;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, s, &d);
+    LaunchCtx x;
+    const int rc = launch_ctx(p, stream, &x);
     if (rc) return rc;
+    hipStream_t s = x.stream;
     const long long need = (n + SDFK_BLOCK - 1) / SDFK_BLOCK;
     const unsigned blocks = (unsigned)std::min<long long>(need, SDFK_VJP_GRID);      // a function of n only
     double* d_ws = nullptr;
     HIPCHK(hipMalloc(&d_ws, ((size_t)blocks + 1) * ns1 * sizeof(double)));
     double* d_sum = d_ws + (size_t)blocks * ns1;
     SrcArray src = {d_co, (long long)row_stride};
-    const int n_instr = (int)(p->code.size() / 2);
     const size_t lds = (size_t)SDFK_VJP_WAVES * ns1 * sizeof(double);
     const int generic = flags & 1;
-    if (p->interp_small)
-        hipLaunchKernelGGL((sdfk_vjp_kernel<SDFK_NC_SMALL, SDFK_NV_SMALL>), dim3(blocks), dim3(SDFK_BLOCK), lds, s, d->d_code,
-                           n_instr, d->d_params, ns, d->d_tables, src, (long long)n, d_in, mode, generic, d_out_value, d_ws,
-                           p->result_reg);
-    else
-        hipLaunchKernelGGL((sdfk_vjp_kernel<SDFK_DUAL_NC, SDFK_DUAL_NV>), dim3(blocks), dim3(SDFK_BLOCK), lds, s, d->d_code,
-                           n_instr, d->d_params, ns, d->d_tables, src, (long long)n, d_in, mode, generic, d_out_value, d_ws,
-                           p->result_reg);
+#define SDFK_VJP_GO(NC, NV) hipLaunchKernelGGL((sdfk_vjp_kernel<NC, NV>), dim3(blocks), dim3(SDFK_BLOCK), lds, s, x.d->d_code, x.n_instr, \
+                                               x.prm, ns, x.tab, src, (long long)n, d_in, mode, generic, d_out_value, d_ws, x.result_reg)
+    SDFK_REGFILE(p, SDFK_DUAL_NC, SDFK_DUAL_NV, SDFK_VJP_GO);
+#undef SDFK_VJP_GO
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(sdfk_vjp_sum_kernel, dim3((ns1 + SDFK_BLOCK - 1) / SDFK_BLOCK), dim3(SDFK_BLOCK), 0, s, d_ws,

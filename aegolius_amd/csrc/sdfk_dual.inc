@@ -239,22 +239,16 @@ extern "C" int sdfk_eval_jvp_device(sdfk_program* p, const float* d_co, int64_t 
     const int chk = sdfk_program_jvp_check(p, &bad);
     if (chk) return fail(chk < 0 ? chk : -3, "sdfk_eval_jvp_device: " + g_err);
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, s, &d);
+    LaunchCtx x;
+    const int rc = launch_ctx(p, stream, &x);
     if (rc) return rc;
     const unsigned blocks = (unsigned)((n + SDFK_BLOCK - 1) / SDFK_BLOCK);
     SrcArray src = {d_co, (long long)row_stride};
-    const int n_instr = (int)(p->code.size() / 2);
     const int ns = (int)p->params.size();
-    if (p->interp_small)
-        launch_jvp<SDFK_NC_SMALL, SDFK_NV_SMALL>(k, blocks, s, d->d_code, n_instr, d->d_params, d_dparams, ns, d->d_tables,
-                                                 src, n, seed_points, d_value, d_tangent, tangent_stride, p->result_reg);
-    else
-        launch_jvp<SDFK_DUAL_NC, SDFK_DUAL_NV>(k, blocks, s, d->d_code, n_instr, d->d_params, d_dparams, ns, d->d_tables, src, n,
-                                     seed_points, d_value, d_tangent, tangent_stride, p->result_reg);
+#define SDFK_JVP_GO(NC, NV) launch_jvp<NC, NV>(k, blocks, x.stream, x.d->d_code, x.n_instr, x.prm, d_dparams, ns, x.tab, src, n, \
+                                               seed_points, d_value, d_tangent, tangent_stride, x.result_reg)
+    SDFK_REGFILE(p, SDFK_DUAL_NC, SDFK_DUAL_NV, SDFK_JVP_GO);
+#undef SDFK_JVP_GO
     HIPCHK(hipGetLastError());
     return 0;
 }

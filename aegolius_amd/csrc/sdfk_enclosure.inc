@@ -261,14 +261,12 @@ extern "C" int sdfk_program_box_check(sdfk_program* p, int* first_bad_op) {
 }
 
 // the checks and the residency every enclosure launch shares
-static int box_prepare(sdfk_program* p, const char* who, hipStream_t s, DevState** d) {
+static int box_prepare(sdfk_program* p, const char* who, void* stream, LaunchCtx* x) {
     if (!p) return fail(-1, "null program");
     int bad = -1;
     const int chk = sdfk_program_box_check(p, &bad);
     if (chk) return fail(chk < 0 ? chk : -3, std::string(who) + ": " + g_err);
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    return ensure_resident(p, device, s, d);
+    return launch_ctx(p, stream, x);
 }
 
 extern "C" int sdfk_enclose_boxes_device(sdfk_program* p, const float* d_lo, const float* d_hi, int64_t n, int64_t stride,
@@ -276,21 +274,16 @@ extern "C" int sdfk_enclose_boxes_device(sdfk_program* p, const float* d_lo, con
     if (n < 0 || stride < n) return fail(-1, "sdfk_enclose_boxes_device: row stride smaller than the box count");
     if (n > 0 && (!d_lo || !d_hi || !d_factors || !d_out_lo || !d_out_hi))
         return fail(-1, "sdfk_enclose_boxes_device: null device pointer");
-    hipStream_t s = (hipStream_t)stream;
-    DevState* d = nullptr;
-    const int rc = box_prepare(p, "sdfk_enclose_boxes_device", s, &d);
+    LaunchCtx x;
+    const int rc = box_prepare(p, "sdfk_enclose_boxes_device", stream, &x);
     if (rc) return rc;
     if (n == 0) return 0;
     const unsigned blocks = (unsigned)((n + SDFK_BLOCK - 1) / SDFK_BLOCK);
-    const int n_instr = (int)(p->code.size() / 2);
-    if (p->interp_small)
-        hipLaunchKernelGGL((sdfk_enclose_kernel<SDFK_NC_SMALL, SDFK_NV_SMALL>), dim3(blocks), dim3(SDFK_BLOCK), 0, s, d->d_code,
-                           n_instr, d->d_params, d_factors, d->d_tables, d_lo, d_hi, (long long)stride, (long long)n, d_out_lo,
-                           d_out_hi, p->result_reg);
-    else
-        hipLaunchKernelGGL((sdfk_enclose_kernel<SDFK_DUAL_NC, SDFK_DUAL_NV>), dim3(blocks), dim3(SDFK_BLOCK), 0, s, d->d_code,
-                           n_instr, d->d_params, d_factors, d->d_tables, d_lo, d_hi, (long long)stride, (long long)n, d_out_lo,
-                           d_out_hi, p->result_reg);
+#define SDFK_ENCLOSE_GO(NC, NV) hipLaunchKernelGGL((sdfk_enclose_kernel<NC, NV>), dim3(blocks), dim3(SDFK_BLOCK), 0, x.stream, x.d->d_code, \
+                                                   x.n_instr, x.prm, d_factors, x.tab, d_lo, d_hi, (long long)stride, (long long)n,    \
+                                                   d_out_lo, d_out_hi, x.result_reg)
+    SDFK_REGFILE(p, SDFK_DUAL_NC, SDFK_DUAL_NV, SDFK_ENCLOSE_GO);
+#undef SDFK_ENCLOSE_GO
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -312,28 +305,22 @@ extern "C" int sdfk_enclose_octree_device(sdfk_program* p, const uint64_t* d_key
         if (!(std::isfinite(dom.lo[a]) && std::isfinite(dom.hi[a]) && dom.lo[a] <= dom.hi[a]))
             return fail(-1, "sdfk_enclose_octree_device: the domain must be finite and ordered");
     }
-    hipStream_t s = (hipStream_t)stream;
-    DevState* d = nullptr;
-    const int rc = box_prepare(p, "sdfk_enclose_octree_device", s, &d);
+    LaunchCtx x;
+    const int rc = box_prepare(p, "sdfk_enclose_octree_device", stream, &x);
     if (rc) return rc;
+    hipStream_t s = x.stream;
     SdfkBoxStats st = {};
     for (int a = 0; a < 3; ++a) st.mn[a] = 0x7fffffff, st.mx[a] = -1;
     if (n > 0) {
         HIPCHK(hipMemcpyAsync(d_scratch, &st, sizeof st, hipMemcpyHostToDevice, s));
         const unsigned blocks = (unsigned)((n + SDFK_BLOCK - 1) / SDFK_BLOCK);
-        const int n_instr = (int)(p->code.size() / 2);
-        if (p->interp_small)
-            hipLaunchKernelGGL((sdfk_enclose_octree_kernel<SDFK_NC_SMALL, SDFK_NV_SMALL>), dim3(blocks), dim3(SDFK_BLOCK), 0, s,
-                               d->d_code, n_instr, d->d_params, d_factors, d->d_tables, p->result_reg,
-                               (const unsigned long long*)d_keys, (long long)n, dom, dims, level, d_status,
-                               (unsigned long long*)(capacity > 0 ? d_children : nullptr), (long long)capacity,
-                               (SdfkBoxStats*)d_scratch);
-        else
-            hipLaunchKernelGGL((sdfk_enclose_octree_kernel<SDFK_DUAL_NC, SDFK_DUAL_NV>), dim3(blocks), dim3(SDFK_BLOCK), 0, s,
-                               d->d_code, n_instr, d->d_params, d_factors, d->d_tables, p->result_reg,
-                               (const unsigned long long*)d_keys, (long long)n, dom, dims, level, d_status,
-                               (unsigned long long*)(capacity > 0 ? d_children : nullptr), (long long)capacity,
-                               (SdfkBoxStats*)d_scratch);
+#define SDFK_OCTREE_GO(NC, NV) hipLaunchKernelGGL((sdfk_enclose_octree_kernel<NC, NV>), dim3(blocks), dim3(SDFK_BLOCK), 0, s, x.d->d_code, \
+                                                  x.n_instr, x.prm, d_factors, x.tab, x.result_reg, (const unsigned long long*)d_keys, \
+                                                  (long long)n, dom, dims, level, d_status,                                      \
+                                                  (unsigned long long*)(capacity > 0 ? d_children : nullptr), (long long)capacity, \
+                                                  (SdfkBoxStats*)d_scratch)
+        SDFK_REGFILE(p, SDFK_DUAL_NC, SDFK_DUAL_NV, SDFK_OCTREE_GO);
+#undef SDFK_OCTREE_GO
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&st, d_scratch, sizeof st, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));

@@ -376,23 +376,40 @@ static int flags_finish(const SelGeom& g, const SelScratch& sc, int64_t* d_index
     if ((int64_t)total > capacity) return fail(-1, "sdfk_eval_select: index buffer smaller than the selection");
     return 0;
 }
-// which layout will the evaluation write? (the same test as run(): the row-block kernels when the program has cull sites
-// and the rows fit their geometry, the plain kernels otherwise)
-static bool select_tiled(const sdfk_program* p, long long n, long long row_len, int mode) {
-    RowGeom rg;
-    return !p->sites.empty() && mode != SDFK_MODE_NOCULL && row_len > 0 && rows_geometry(n, row_len, &rg);
-}
-static int select_prepare(const SelGeom& g, float threshold, void* d_scratch, hipStream_t stream, SelScratch* sc, unsigned* thr) {
+// Plans the evaluation of a fused selection and lays its flag words out from that plan: the row-block kernels write the
+// tiled layout, the plain kernels the linear one — the kernel that writes the flags and the code that reads them take the
+// layout from this one plan. row_len: the rows of the tiled layout (an array's hint, a grid's rows). On return c->plan,
+// c->d_flags and c->thr_key are set and the words the kernels do not write are cleared.
+static int select_prepare(EvalCall* c, EvalPlan* pl, long long row_len, float threshold, void* d_scratch, SelGeom* g, SelScratch* sc) {
     if (!d_scratch || ((uintptr_t)d_scratch & 7)) return fail(-1, "sdfk_eval_select: the scratch must be 8-byte aligned device memory");
-    *sc = sel_scratch(d_scratch, g);
-    *thr = sdfk_sel_key(threshold);
+    c->d_flags = static_cast<unsigned*>(d_scratch);            // (the planner asks whether flags are written; where follows from the plan)
+    const int rc = plan_eval(*c, plan_env(), pl);
+    if (rc) return rc;
+    *g = sel_geom(c->n, row_len, pl->rows());
+    *sc = sel_scratch(d_scratch, *g);
+    c->plan = pl;
+    c->d_flags = sc->flags;
+    c->thr_key = sdfk_sel_key(threshold);
+    hipStream_t stream = (hipStream_t)c->stream;
     // Linear layout (plain kernels): single points OR their bits in (tails, unaligned arrays), so the words start from zero.
     // Tiled layout (row-block kernels): every slot word of every block is written by exactly one brick — rows past the end
     // of the last block as zeros —, so only the padding behind the last block is cleared (round 3 cleared all n / 8 bytes:
     // 135 MB at 1025^3 in front of every selection).
-    if (g.RB == 16) HIPCHK(hipMemsetAsync(sc->flags + sel_words(g), 0, 64 * sizeof(unsigned), stream));
-    else HIPCHK(hipMemsetAsync(sc->flags, 0, (size_t)(sel_words(g) + 64) * sizeof(unsigned), stream));
+    if (g->RB == 16) HIPCHK(hipMemsetAsync(sc->flags + sel_words(*g), 0, 64 * sizeof(unsigned), stream));
+    else HIPCHK(hipMemsetAsync(sc->flags, 0, (size_t)(sel_words(*g) + 64) * sizeof(unsigned), stream));
     return 0;
+}
+// the evaluation writes the flags, then count, scan, (optionally) scatter
+static int select_run(const EvalCall& c, const SelGeom& g, const SelScratch& sc, int64_t* d_index, int64_t capacity, int64_t* count) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    if (c.thr_key == 0xffffffffu) {                            // NaN threshold: nothing compares <= NaN
+        HIPCHK(hipMemsetAsync(sc.blk, 0, (size_t)(sc.tiles + 1) * sizeof(unsigned long long), stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    const int rc = run(c);
+    if (rc) return rc;
+    return flags_finish(g, sc, d_index, capacity, count, stream);
 }
 
 extern "C" int sdfk_eval_device_select(sdfk_program* p, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
@@ -404,23 +421,16 @@ extern "C" int sdfk_eval_device_select(sdfk_program* p, const float* d_co, int64
     if (p->n_aux > 0) return fail(-1, "sdfk_eval_device_select: staged programs (auxiliary fields) are evaluated to a field first");
     *count = 0;
     if (n == 0) return 0;
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    hipStream_t stream = (hipStream_t)stream_;
-    const SelGeom g = sel_geom(n, row_len, select_tiled(p, n, row_len, mode));
-    SelScratch sc;
-    unsigned thr = 0;
-    int rc = select_prepare(g, threshold, d_scratch, stream, &sc, &thr);
-    if (rc) return rc;
-    if (thr == 0xffffffffu) {                                  // NaN threshold: nothing compares <= NaN
-        HIPCHK(hipMemsetAsync(sc.blk, 0, (size_t)(sc.tiles + 1) * sizeof(unsigned long long), stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
-    }
     SrcArray a = {d_co, (long long)row_stride};
-    const bool vec_ok = aligned16(d_co) && (row_stride % 4 == 0);
-    rc = run(p, &a, nullptr, n, nullptr, stream_, mode, vec_ok, g.RB == 16 ? row_len : 0, nullptr, 0, flat != 0, 0, 0, sc.flags, thr);
+    EvalCall c = array_call(p, &a, n, nullptr, stream_, mode, aligned16(d_co) && (row_stride % 4 == 0));
+    c.row_len = row_len;
+    c.flat = flat != 0;
+    EvalPlan pl;
+    SelGeom g;
+    SelScratch sc;
+    const int rc = select_prepare(&c, &pl, row_len, threshold, d_scratch, &g, &sc);
     if (rc) return rc;
-    return flags_finish(g, sc, d_index, capacity, count, stream);
+    return select_run(c, g, sc, d_index, capacity, count);
 }
 
 extern "C" int sdfk_eval_grid_select(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
@@ -432,39 +442,35 @@ extern "C" int sdfk_eval_grid_select(sdfk_program* p, const float* ax0, int64_t 
     if (p->n_aux > 0) return fail(-1, "sdfk_eval_grid_select: staged programs (auxiliary fields) are evaluated to a field first");
     *count = 0;
     if (n == 0) return 0;
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    hipStream_t stream = (hipStream_t)stream_;
-    const long long grow = n2 > 1 ? n2 : n1;                   // the grid's rows (run() makes the same choice)
-    const bool tiled = start % grow == 0 && select_tiled(p, n, grow, mode);
-    const SelGeom g = sel_geom(n, grow, tiled);
-    SelScratch sc;
-    unsigned thr = 0;
-    int rc = select_prepare(g, threshold, d_scratch, stream, &sc, &thr);
-    if (rc) return rc;
-    if (thr == 0xffffffffu) {
-        HIPCHK(hipMemsetAsync(sc.blk, 0, (size_t)(sc.tiles + 1) * sizeof(unsigned long long), stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
-    }
     AxisTables t;
     SrcGrid sg;
-    rc = upload_axes(ax0, n0, ax1, n1, ax2, n2, stream, &t, &sg, start);
+    int rc = upload_axes(ax0, n0, ax1, n1, ax2, n2, (hipStream_t)stream_, &t, &sg, start);
     if (rc) return rc;
-    rc = run(p, nullptr, &sg, n, nullptr, stream_, mode, true, 0, nullptr, 0, false, 0, 0, sc.flags, thr);
+    EvalCall c = grid_call(p, &sg, n, nullptr, stream_, mode, true);
+    EvalPlan pl;
+    SelGeom g;
+    SelScratch sc;
+    rc = select_prepare(&c, &pl, n2 > 1 ? n2 : n1, threshold, d_scratch, &g, &sc);
     if (rc) return rc;
-    return flags_finish(g, sc, d_index, capacity, count, stream);   // (synchronises: the axis tables go)
+    return select_run(c, g, sc, d_index, capacity, count);     // (synchronises: the axis tables go)
 }
 
 // Second half of a fused selection whose count-only call (d_index == NULL) has just run with the same arguments: the
-// indices, from the flags. row_len / tiled layout are re-derived the same way, so the caller passes what it passed before.
+// indices, from the flags. There are no coordinates here: the layout is that of the plan of the same (n, row_len, mode).
 extern "C" int sdfk_eval_select_finish(sdfk_program* p, int64_t n, int64_t row_len, int mode, int64_t count, int64_t* d_index,
                                        int64_t capacity, void* d_scratch, void* stream_) {
     if (!p || n < 0 || count < 0 || capacity < 0 || !d_scratch || ((uintptr_t)d_scratch & 7))
         return fail(-1, "sdfk_eval_select_finish: bad arguments");
     if (n == 0 || count == 0) return 0;
     if (!d_index || count > capacity) return fail(-1, "sdfk_eval_select_finish: index buffer smaller than the selection");
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    const SelGeom g = sel_geom(n, row_len, select_tiled(p, n, row_len, mode));
+    const SrcArray a = {nullptr, 0};
+    EvalCall c = array_call(p, &a, n, nullptr, stream_, mode, false);
+    c.row_len = row_len;
+    c.d_flags = static_cast<unsigned*>(d_scratch);
+    EvalPlan pl;
+    const int rc = plan_eval(c, plan_env(), &pl);
+    if (rc) return rc;
+    const SelGeom g = sel_geom(n, row_len, pl.rows());
     const SelScratch sc = sel_scratch(d_scratch, g);
     unsigned long long total = 0;
     HIPCHK(hipMemcpy(&total, sc.blk + sc.tiles, sizeof total, hipMemcpyDeviceToHost));

@@ -400,7 +400,7 @@ struct MeshSrc {
     int mode;
 };
 
-// the geometry path's grid: rows along the last axis longer than one point, as run() and sdfk_eval_grid_select take them
+// the geometry path's grid: rows along the last axis longer than one point, as plan_eval and sdfk_eval_grid_select take them
 static long long mesh_grow(int D, const int64_t* dims) { return D == 3 ? dims[2] : dims[1]; }
 // bytes of the brick-tiled flag slots the evaluation may write, with the padding select_prepare clears (0: rows too short
 // for the row-block kernels, whose flags are the linear bit string itself)
@@ -425,7 +425,6 @@ static void mesh_scratch(int D, const int64_t* dims, const MeshGeom& g, const Me
 template <int D>
 static int mesh_eval_bits(const MeshSrc& src, const int64_t* dims, const MeshGeom& g, const MeshScratch& sc, float level,
                           hipStream_t stream, const char* who) {
-    int mode = src.mode == SDFK_MODE_AUTO ? g_default_mode : src.mode;
     const long long grow = mesh_grow(D, dims), rows = g.n / grow;
     // Slabs of whole rows, at most 2^32 points each: a launch holds fewer than 2^32 work-items (the row-block kernel's
     // tiles x threads passed that at 4097^3, and the plain kernel's n / 4 from 2^34 points on). A slab starts at a
@@ -433,22 +432,29 @@ static int mesh_eval_bits(const MeshSrc& src, const int64_t* dims, const MeshGeo
     // (row0 * nchunk words); linear, row0 * grow / 32 words. (The layout is that of every slab: the first is the largest.)
     const long long slab = std::max(32ll, ((1ll << 32) / grow) & ~31ll);
     if (slab * grow > (1ll << 32)) return fail(-1, std::string(who) + ": rows longer than 2^27 points");
-    const bool tiled = select_tiled(src.prog, std::min(slab, rows) * grow, grow, mode);
-    const SelGeom sg = sel_geom(g.n, grow, tiled);
-    unsigned* flags = tiled ? reinterpret_cast<unsigned*>(sc.rec) : sc.bits;
-    if (tiled) HIPCHK(hipMemsetAsync(flags + sel_words(sg), 0, 64 * sizeof(unsigned), stream));
-    else HIPCHK(hipMemsetAsync(sc.bits, 0, (size_t)g.words * sizeof(unsigned), stream));
     SrcGrid grid;
     grid.ax0 = sc.axes;
     grid.ax1 = sc.axes + dims[0];
     grid.ax2 = sc.axes + dims[0] + dims[1];                    // (2-D: the 0.0 behind the two tables)
     grid.n1 = (unsigned)dims[1];
     grid.n2 = D == 3 ? (unsigned)dims[2] : 1u;
+    grid.start = 0;
+    EvalCall c = grid_call(src.prog, &grid, std::min(slab, rows) * grow, nullptr, stream, src.mode, true);
+    c.d_flags = sc.bits;                                       // (the planner asks whether flags are written; where is set per slab)
+    c.thr_key = sdfk_sel_key(level);
+    EvalPlan first;                                            // the layout is that of every slab: the first is the largest
+    int rc = plan_eval(c, plan_env(), &first);
+    if (rc) return rc;
+    const bool tiled = first.rows();
+    const SelGeom sg = sel_geom(g.n, grow, tiled);
+    unsigned* flags = tiled ? reinterpret_cast<unsigned*>(sc.rec) : sc.bits;
+    if (tiled) HIPCHK(hipMemsetAsync(flags + sel_words(sg), 0, 64 * sizeof(unsigned), stream));
+    else HIPCHK(hipMemsetAsync(sc.bits, 0, (size_t)g.words * sizeof(unsigned), stream));
     for (long long row0 = 0; row0 < rows; row0 += slab) {
-        const long long m = std::min(slab, rows - row0) * grow;
+        c.n = std::min(slab, rows - row0) * grow;
         grid.start = row0 * grow;
-        unsigned* f0 = flags + (tiled ? row0 * (long long)sg.nchunk : row0 * grow / 32);
-        int rc = run(src.prog, nullptr, &grid, m, nullptr, stream, mode, true, 0, nullptr, 0, false, 0, 0, f0, sdfk_sel_key(level));
+        c.d_flags = flags + (tiled ? row0 * (long long)sg.nchunk : row0 * grow / 32);
+        rc = run(c);
         if (rc) return rc;
     }
     if (tiled)
@@ -559,7 +565,7 @@ static int mesh_finish(const MeshSrc& src, const int64_t* dims, float level, int
         // the 2 V ends in chunks of 2^32 points (launch sizes, as the slabs of mesh_eval_bits); rows of es floats
         for (long long off = 0; off < 2 * nv; off += 1ll << 32) {
             SrcArray a = {static_cast<const float*>(ends.p) + off, es};
-            rc = run(src.prog, &a, nullptr, std::min(2 * nv - off, 1ll << 32), vals + off, stream, src.mode, true);
+            rc = run(array_call(src.prog, &a, std::min(2 * nv - off, 1ll << 32), vals + off, stream, src.mode, true));
             if (rc) return rc;
         }
         const long long blocks = std::min<long long>((nv + 255) / 256, 1ll << 20);

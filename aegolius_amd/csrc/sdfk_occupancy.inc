@@ -238,11 +238,13 @@ extern "C" int sdfk_eval_grid_occupancy(sdfk_program* p, const float* ax0, int64
     const int64_t total_cells = n0 * n1 * n2;
     const int64_t slab = occ_slab_cells(n0, n1, n2, slab_cells);
 
-    hipStream_t stream = (hipStream_t)stream_;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, stream, &d);
+    LaunchCtx x;
+    int rc = launch_ctx(p, stream_, &x);
+    if (rc) return rc;
+    hipStream_t stream = x.stream;
+    // the sample pass's kernel, the same for every slab (a failed build falls back in AUTO only)
+    std::shared_ptr<SpecModule> sk;
+    rc = pick_kernel(p, x.device, SDFK_FL_OCCUPANCY, 0, mode, mode == SDFK_MODE_AUTO, "occupancy kernel", false, &sk);
     if (rc) return rc;
 
     // tables: the axis tables as sdfk_eval_grid uploads them, then the sub-sample tables and the half-widths
@@ -277,9 +279,8 @@ extern "C" int sdfk_eval_grid_occupancy(sdfk_program* p, const float* ax0, int64
                       lg(k0) + lg(k1) + lg(k2), 1.0f / (float)K, sdfk_sel_key(level), total_cells < (1LL << 32) ? 1u : 0u, 0};
     sdfk_occclass C = {g.ax0, g.ax1, g.ax2, d_hw[0], d_hw[1], d_hw[2], (unsigned)n1, (unsigned)n2, 0, 0, level, lipschitz,
                        sdfk_sel_key(level)};
-    const float* prm = d->d_params;
-    const float* tab = d->d_tables;
-    const int n_instr = (int)(p->code.size() / 2);
+    const float* prm = x.prm;
+    const float* tab = x.tab;
     const unsigned per_wave = K >= 64u ? 1u : 64u / K;          // entries of one wave (sdfk_occdev.h)
     int64_t near_total = 0;
 
@@ -290,7 +291,7 @@ extern "C" int sdfk_eval_grid_occupancy(sdfk_program* p, const float* ax0, int64
         if (pass_ms) HIPCHK(hipEventRecord(ev.e[0], stream));
         if (skip) {
             g.start = first;
-            rc = run(p, nullptr, &g, cells, d_centre, stream, mode, true);
+            rc = run(grid_call(p, &g, cells, d_centre, stream, mode, true));
             if (rc) return rc;
             if (pass_ms) HIPCHK(hipEventRecord(ev.e[1], stream));
             C.first = first;
@@ -317,20 +318,6 @@ extern "C" int sdfk_eval_grid_occupancy(sdfk_program* p, const float* ax0, int64
             G.first = first;
             const unsigned long long waves = (n_entries + per_wave - 1) / per_wave;
             const unsigned blocks = (unsigned)((waves + SDFK_OCC_BLOCK / 64 - 1) / (SDFK_OCC_BLOCK / 64));
-            std::shared_ptr<SpecModule> sk;
-            if (mode != SDFK_MODE_INTERPRET) {                     // (as rays_run: AUTO is served by the interpreter kernel
-                static const bool async_jit = [] { const char* e = getenv("SDFK_ASYNC_JIT"); return !(e && e[0] == '0'); }();
-                const bool wait = mode != SDFK_MODE_AUTO || !p->interp_ok || !async_jit;   //  while the build runs)
-                std::string err;
-                sk = get_module(p, device, SDFK_FL_OCCUPANCY, wait, &err);
-                if (sk && sk->failed) {
-                    if (mode != SDFK_MODE_AUTO || !p->interp_ok)
-                        return fail(-3, "specialised occupancy kernel unavailable: " + err);
-                    sk.reset();
-                }
-            }
-            if (!sk && !p->interp_ok)
-                return fail(-4, "program needs more registers than the interpreter kernel has (use the specialised mode)");
             SdfkOccList src_list = {d_list, n_entries};
             SdfkOccAll src_all = {n_entries};
             if (sk) {
@@ -340,12 +327,10 @@ extern "C" int sdfk_eval_grid_occupancy(sdfk_program* p, const float* ax0, int64
             } else {
                 auto launch = [&](auto src) {
                     using SRC = decltype(src);
-                    if (p->interp_small)
-                        hipLaunchKernelGGL((sdfk_occ_interp_kernel<SDFK_NC_SMALL, SDFK_NV_SMALL, SRC>), dim3(blocks),
-                                           dim3(SDFK_OCC_BLOCK), 0, stream, d->d_code, n_instr, prm, tab, p->result_reg, src, G, out);
-                    else
-                        hipLaunchKernelGGL((sdfk_occ_interp_kernel<SDFK_NC, SDFK_NV, SRC>), dim3(blocks), dim3(SDFK_OCC_BLOCK), 0,
-                                           stream, d->d_code, n_instr, prm, tab, p->result_reg, src, G, out);
+#define SDFK_OCC_GO(NC, NV) hipLaunchKernelGGL((sdfk_occ_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_OCC_BLOCK), 0, stream, \
+                                               x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, G, out)
+                    SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_OCC_GO);
+#undef SDFK_OCC_GO
                 };
                 if (skip) launch(src_list);
                 else launch(src_all);

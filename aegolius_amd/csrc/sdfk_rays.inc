@@ -160,12 +160,10 @@ static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, 
     if (chk) return fail(chk < 0 ? chk : -3, w + ": " + g_err);
     if (count == 0) return 0;
     if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    hipStream_t stream = (hipStream_t)stream_;
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    DevState* d = nullptr;
-    int rc = ensure_resident(p, device, stream, &d);
+    LaunchCtx x;
+    int rc = launch_ctx(p, stream_, &x);
     if (rc) return rc;
+    hipStream_t stream = x.stream;
     unsigned blocks;
     if (cam) {
         const long long tiles = (long long)((cam->width + 7) / 8) * ((cam->height + 7) / 8);
@@ -173,21 +171,11 @@ static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, 
     } else {
         blocks = (unsigned)((count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
     }
-    std::shared_ptr<SpecModule> sk;
-    if (mode != SDFK_MODE_INTERPRET) {                         // (as run(): AUTO is served by the interpreter kernel while
-        static const bool async_jit = [] { const char* e = getenv("SDFK_ASYNC_JIT"); return !(e && e[0] == '0'); }();
-        const bool wait = mode != SDFK_MODE_AUTO || !p->interp_ok || !async_jit;   //  the build runs in the background)
-        std::string err;
-        sk = get_module(p, device, SDFK_FL_RAYS, wait, &err);
-        if (sk && sk->failed) {
-            if (mode != SDFK_MODE_AUTO || !p->interp_ok) return fail(-3, "specialised ray kernel unavailable: " + err);
-            sk.reset();
-        }
-    }
-    if (!sk && !p->interp_ok)
-        return fail(-4, "program needs more registers than the interpreter kernel has (use the specialised mode)");
-    const float* prm = d->d_params;
-    const float* tab = d->d_tables;
+    std::shared_ptr<SpecModule> sk;                            // (a failed build falls back in AUTO only)
+    rc = pick_kernel(p, x.device, SDFK_FL_RAYS, 0, mode, mode == SDFK_MODE_AUTO, "ray kernel", false, &sk);
+    if (rc) return rc;
+    const float* prm = x.prm;
+    const float* tab = x.tab;
     sdfk_rayopts o = opts;
     if (sk) {
         // the culled pair (long chains only) unless the caller asked for the kernel without culling; one more argument,
@@ -212,17 +200,12 @@ static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, 
         }
         return 0;
     }
-    const int n_instr = (int)(p->code.size() / 2);
     auto launch = [&](auto src) {
         using SRC = decltype(src);
-        if (p->interp_small)
-            hipLaunchKernelGGL((sdfk_rays_interp_kernel<SDFK_NC_SMALL, SDFK_NV_SMALL, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK),
-                               0, stream, d->d_code, n_instr, prm, tab, p->result_reg, src, o, d_t, d_status, d_steps,
-                               d_normals, nstride);
-        else
-            hipLaunchKernelGGL((sdfk_rays_interp_kernel<SDFK_NC, SDFK_NV, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream,
-                               d->d_code, n_instr, prm, tab, p->result_reg, src, o, d_t, d_status, d_steps, d_normals,
-                               nstride);
+#define SDFK_RAYS_GO(NC, NV) hipLaunchKernelGGL((sdfk_rays_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream, \
+                                                x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, o, d_t, d_status, d_steps, d_normals, nstride)
+        SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_RAYS_GO);
+#undef SDFK_RAYS_GO
     };
     if (cam) launch(SdfkRaysCamera{*cam});
     else launch(*arr);

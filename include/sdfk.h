@@ -181,7 +181,8 @@ int sdfk_eval_device_rows2d(sdfk_program* prog, const float* d_co, int64_t n, in
  * cores/helper_functions.py:63-75, always appends a row of zeros; streaming it costs a quarter of the traffic: 12
  * instead of 16 bytes per point). row_len as for sdfk_eval_device_rows2d (0: no layout hint — the plain kernel). The
  * field is bit-identical to sdfk_eval_device_rows2d on the same x, y with a zero z row. Waits for the specialised kernel
- * (the interpreter kernel has no two-row build); programs that read auxiliary fields are refused. */
+ * (the interpreter kernel has no two-row build): when that build is unavailable the call returns -3 in EVERY mode, nothing
+ * launched, nothing written; programs that read auxiliary fields are refused. */
 int sdfk_eval_device_rows2d_xy(sdfk_program* prog, const float* d_xy, int64_t n, int64_t row_stride, int64_t row_len,
                                float* d_out, void* stream, int mode);
 /* Host-buffer convenience: stages co (dtype 0 = fp32, 1 = fp64; (3, n) with row stride in elements)
@@ -227,6 +228,16 @@ int sdfk_debug_brick_masks(sdfk_program* prog, const float* d_co, int64_t n, int
  * *brick_rows are returned. */
 int sdfk_debug_row_masks(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len,
                          uint64_t* d_masks, int64_t* n_bricks, int* brick_rows, void* stream);
+/* Test aid: which kernel would an evaluation get? The plan of a request, computed on the host — no device is touched, so
+ * it answers on a machine without one. request, 13 values:
+ *   [0] source: 0 = a coordinate array, 1 = grid tables   [1] points (> 0)        [2] mode (SDFK_MODE_*)
+ *   [3] rows and output 16-byte aligned (0 / 1)            [4] row_len hint        [5] flat hint (0 / 1)
+ *   [6] plane_rows hint   [7] first_row_in_plane hint      [8] flags instead of the field: fused selection (0 / 1)
+ *   [9] two-row coordinates (0 / 1)                        [10] n1, [11] n2, [12] start of a grid ([4]-[7] are an array's)
+ * plan, 4 values: [0] the resolved mode (AUTO only where the call may start on the interpreter kernel; INTERPRET: no
+ * kernel is built), [1] the SDFK_FLAVOUR_* a specialised launch takes, [2] 1 when the call has no interpreter fallback
+ * (flags, two-row coordinates: -3 when the build is unavailable), [3] bricks of a row-block launch (0 for other flavours). */
+int sdfk_debug_eval_plan(sdfk_program* prog, const int64_t* request, int64_t* plan);
 
 /* ---- staged evaluation: grid-neighbourhood modifications ------------------------------------------
  * signed / conv_averaging / conv_edge_detection (cores/modifications.py:220-275, 1589-1637) reshape the field to
@@ -301,7 +312,8 @@ int sdfk_field_select_finish(int64_t n, int64_t count, int64_t* d_index, int64_t
  * the bits are those of sdfk_eval_device's field. Same two-step protocol as sdfk_field_select: d_index == NULL returns
  * the count and keeps the flags in d_scratch (sdfk_eval_select_scratch(n, row_len) bytes of device memory, 8-byte aligned) for
  * sdfk_eval_select_finish. row_len / flat: the layout hints of sdfk_eval_device_rows / _rows2d (0: none). Runs on the
- * specialised kernels (the call waits for their build); programs with auxiliary fields are refused. */
+ * specialised kernels (the call waits for their build, and returns -3 in EVERY mode when that build is unavailable: the
+ * interpreter kernel writes no flags); programs with auxiliary fields are refused. */
 size_t sdfk_eval_select_scratch(int64_t n, int64_t row_len);
 int sdfk_eval_device_select(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, int64_t row_len, int flat,
                             float threshold, int64_t* d_index, int64_t capacity, int64_t* count, void* d_scratch,

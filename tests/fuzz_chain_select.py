@@ -128,7 +128,7 @@ def device_eval(engine, prog, co32, mode, row_len=None, flat=False, misalign=0):
         lib.sdfk_free(vp(d_out))
 
 
-SPECIALIZE_LIMIT = int(os.environ.get("SDFK_SPECIALIZE_LIMIT", "1200"))     # csrc/sdfk.hip, run(): the same default
+SPECIALIZE_LIMIT = int(os.environ.get("SDFK_SPECIALIZE_LIMIT", "1200"))     # csrc/sdfk_launch.inc, plan_env(): the same default
 
 
 def main(first=9000, count=40):
@@ -152,7 +152,7 @@ def main(first=9000, count=40):
         chain_seen += chain
         msg = []
         if not chain and low.code.shape[0] > SPECIALIZE_LIMIT:
-            # a program that is no chain and lies beyond SDFK_SPECIALIZE_LIMIT (csrc/sdfk.hip: the size up to which a
+            # a program that is no chain and lies beyond SDFK_SPECIALIZE_LIMIT (csrc/sdfk_launch.inc: the size up to which a
             # specialised kernel is built within the build budget): the product serves it from the interpreter kernel,
             # which is what is checked — against the oracle, every sampled point
             out = device_eval(_engine, prog, co32, _engine.MODE_INTERPRET)

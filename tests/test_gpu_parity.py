@@ -1176,6 +1176,44 @@ def test_two_row_coordinates_equal_the_three_row_path(shape, engine):
         assert torch.equal(outs[0][:n], outs[1][:n])
 
 
+def test_two_row_coordinates_never_reach_the_interpreter_kernel(engine):
+    """Two-row coordinates have no interpreter form (that kernel reads a third row): when the specialised build is
+    unavailable — here: a -D switch no build survives — the call returns -3 in EVERY mode and writes nothing, NOCULL and
+    AUTO included, which otherwise fall back on the interpreter kernel. The two rows are the head of a zero-padded
+    three-row buffer, so a wrong fallback would read valid memory and fill the output instead of faulting. 17 rows of 33
+    points: two blocks of rows, the second partial, rows that are no multiple of 32."""
+    import torch
+    from test_native_cpu import REJECTING_DEFS
+    n0, n1 = 17, 33
+    n, stride = n0 * n1, 576
+    co = torch.zeros((3, stride), dtype=torch.float32, device="cuda")
+    co[0, :n] = torch.from_numpy(np.repeat(np.linspace(-1, 1, n0).astype(np.float32), n1)).cuda()
+    co[1, :n] = torch.from_numpy(np.tile(np.linspace(-1, 1, n1).astype(np.float32), n0)).cuda()
+    circle = ns.Circle(0.8)
+    circle.onion(0.1)
+    circle.move((0.3, -0.2, 0))
+    prog = engine.Program.from_lowered(lower_geometry(circle))     # a fresh program: no module of it is loaded yet
+    out = torch.full((stride,), float("nan"), dtype=torch.float32, device="cuda")
+    modes = (engine.MODE_NOCULL, engine.MODE_SPECIALIZED, engine.MODE_AUTO)
+    engine.lib().sdfk_debug_set_rtc_defs(REJECTING_DEFS)
+    try:
+        for mode in modes:
+            for row_len in (n1, None):
+                with pytest.raises(engine.SdfkError, match=r"\(-3\): specialised kernel unavailable"):
+                    prog.eval_device_xy(co.data_ptr(), n, stride, out.data_ptr(), mode=mode, row_len=row_len)
+                torch.cuda.synchronize()
+                assert bool(torch.isnan(out).all()), (mode, row_len)
+    finally:
+        engine.lib().sdfk_debug_set_rtc_defs(b"")
+    want = torch.empty((stride,), dtype=torch.float32, device="cuda")
+    prog.eval_device(co.data_ptr(), n, stride, want.data_ptr(), mode=engine.MODE_SPECIALIZED)
+    for mode in modes:
+        out.fill_(float("nan"))
+        prog.eval_device_xy(co.data_ptr(), n, stride, out.data_ptr(), mode=mode)
+        torch.cuda.synchronize()
+        assert torch.equal(out[:n], want[:n]), mode
+
+
 def _placed2d(rng):
     o = [ns.Circle(0.4), ns.Rectangle(0.8, 0.5), ns.NGon(0.4, 6)][int(rng.integers(0, 3))]
     o.rotate(float(rng.uniform(0, np.pi)), (0, 0, 1))

@@ -459,7 +459,7 @@ print(json.dumps(dict(instructions=int(low.code.shape[0]), size=size, builds=_en
 
 def test_big_programs_are_built_with_their_own_compiler_options(built, tmp_path):
     """From SDFK_BIG_PROGRAM instructions on (300) a program that is no chain is built without the two LLVM passes whose
-    time grows with the square of the program (csrc/sdfk.hip rtc_options): the options reach hiprtc through the compiler
+    time grows with the square of the program (csrc/sdfk_jit.inc rtc_options): the options reach hiprtc through the compiler
     child process, and they are part of the cache key — the same program under another threshold is another file."""
     import json
     import subprocess
@@ -511,3 +511,204 @@ def test_a_process_that_leaves_does_not_wait_for_a_running_build(built, tmp_path
     took = time.time() - t0
     assert "LEAVING" in res.stdout and "BUILT" not in res.stdout, res.stdout + res.stderr[-300:]
     assert took < 12.0, took                                       # (import + 2 s of sleep + the kill; the build alone: > 20 s)
+
+
+# ---- the evaluation planner (csrc/sdfk_launch.inc plan_eval) through sdfk_debug_eval_plan: no device involved ------------------
+_AUTO, _INTERPRET, _SPECIALIZED, _NOCULL = 0, 1, 2, 3
+(_PLAIN_ARRAY, _PLAIN_GRID, _TILE_ARRAY, _TILE_GRID, _TILE_MASK, _ROWS_ARRAY, _ROWS_GRID, _ROWS_MASK, _ROWS2D_ARRAY,
+ _ROWS2D_GRID) = range(10)
+_ROWS, _LEN = 17, 33                    # rows of 33 points: >= 32, no multiple of 32; 17 rows: one full block of 16 and a partial one
+_N = _ROWS * _LEN                       # 2 windows of 32 points per row x 2 blocks = 4 bricks
+
+
+def _plan(engine, prog, *, grid=None, n=_N, mode=_AUTO, vec_ok=True, row_len=0, flat=False, plane_rows=0, phase=0,
+          flags=False, xy=False):
+    """-> (resolved mode, flavour, needs_specialised, bricks) of one request; grid = (n1, n2, start)."""
+    import ctypes
+    n1, n2, start = grid if grid else (0, 0, 0)
+    req = (ctypes.c_int64 * 13)(1 if grid else 0, n, mode, int(vec_ok), row_len, int(flat), plane_rows, phase, int(flags), int(xy),
+                                n1, n2, start)
+    out = (ctypes.c_int64 * 4)()
+    engine.check(engine.lib().sdfk_debug_eval_plan(prog.handle, req, out), "sdfk_debug_eval_plan")
+    return tuple(out)
+
+
+def _plan_programs(engine):
+    import aegolius_amd.cores as ns
+    from aegolius_amd import workloads
+    from aegolius_amd._lower import lower_geometry
+    bare = engine.Program.from_lowered(lower_geometry(ns.Sphere(0.5)))                     # no cull sites
+    tree = engine.Program.from_lowered(lower_geometry(workloads.cfg2_tree(ns, seed=11)))   # 9 sites, 29 instructions
+    chain = engine.Program.from_lowered(lower_geometry(workloads.cfg4_scene2d(ns)))        # a 50-member hard union: chain mode
+    assert chain.chain_members == 50 and tree.chain_members == 0
+    return bare, tree, chain
+
+
+def test_the_evaluation_plan_of_every_kind_of_request(built):
+    """Which kernel family a call gets, which mode it resolves to and whether it may fall back on the interpreter kernel.
+    The expected plans are read off the decision as it stood inline in the evaluation runner before the planner existed
+    (row blocks > line bricks > plain; NOCULL and programs without sites: plain; flags and two-row coordinates force the
+    specialised kernels and never take line bricks; chain mode has no line bricks and blocks rows per grid plane)."""
+    bare, tree, chain = _plan_programs(built)
+    P = lambda prog, **kw: _plan(built, prog, **kw)
+    # no cull sites: plain in every mode, whatever the hints
+    for mode in (_AUTO, _INTERPRET, _SPECIALIZED, _NOCULL):
+        assert P(bare, mode=mode, row_len=_LEN) == (mode, _PLAIN_ARRAY, 0, 0)
+        assert P(bare, mode=mode, grid=(_ROWS, _LEN, 0)) == (mode, _PLAIN_GRID, 0, 0)
+    # sites + array + row hint: row blocks; flat or two-row coordinates: the flat build
+    for mode in (_AUTO, _SPECIALIZED):
+        assert P(tree, mode=mode, row_len=_LEN) == (mode, _ROWS_ARRAY, 0, 4)
+        assert P(tree, mode=mode, row_len=_LEN, vec_ok=False) == (mode, _ROWS_ARRAY, 0, 4)
+        assert P(tree, mode=mode, row_len=_LEN, flat=True) == (mode, _ROWS2D_ARRAY, 0, 4)
+    assert P(tree, row_len=_LEN, flat=True, xy=True) == (_SPECIALIZED, _ROWS2D_ARRAY, 1, 4)
+    assert P(tree, row_len=_LEN, xy=True) == (_SPECIALIZED, _ROWS2D_ARRAY, 1, 4)
+    assert P(tree, row_len=31, n=17 * 31) == (_AUTO, _TILE_ARRAY, 0, 0)                    # rows shorter than 32 points: no row blocks
+    # sites + array + no hint: line bricks when 16-byte accesses are safe, else plain
+    assert P(tree) == (_AUTO, _TILE_ARRAY, 0, 0)
+    assert P(tree, vec_ok=False) == (_AUTO, _PLAIN_ARRAY, 0, 0)
+    # NOCULL: plain; INTERPRET: no kernel is built
+    assert P(tree, mode=_NOCULL, row_len=_LEN) == (_NOCULL, _PLAIN_ARRAY, 0, 0)
+    assert P(tree, mode=_NOCULL, grid=(_ROWS, _LEN, 0)) == (_NOCULL, _PLAIN_GRID, 0, 0)
+    assert P(tree, mode=_INTERPRET, row_len=_LEN)[0] == _INTERPRET
+    assert P(tree, mode=_INTERPRET, grid=(_ROWS, _LEN, 0))[0] == _INTERPRET
+    # flags instead of the field: the specialised kernels, no interpreter fallback, never line bricks
+    for mode in (_AUTO, _INTERPRET, _SPECIALIZED):
+        assert P(tree, mode=mode, flags=True, row_len=_LEN) == (_SPECIALIZED, _ROWS_ARRAY, 1, 4)
+        assert P(tree, mode=mode, flags=True) == (_SPECIALIZED, _PLAIN_ARRAY, 1, 0)
+        assert P(tree, mode=mode, flags=True, grid=(_ROWS, _LEN, 5), n=_LEN) == (_SPECIALIZED, _PLAIN_GRID, 1, 0)
+    assert P(tree, mode=_NOCULL, flags=True, row_len=_LEN) == (_NOCULL, _PLAIN_ARRAY, 1, 0)
+    # two-row coordinates: the same, in every mode (NOCULL keeps its mode and still has no fallback)
+    for mode in (_AUTO, _INTERPRET, _SPECIALIZED):
+        assert P(tree, mode=mode, xy=True) == (_SPECIALIZED, _PLAIN_ARRAY, 1, 0)
+    assert P(tree, mode=_NOCULL, xy=True, row_len=_LEN, flat=True) == (_NOCULL, _PLAIN_ARRAY, 1, 0)
+    assert P(bare, xy=True) == (_SPECIALIZED, _PLAIN_ARRAY, 1, 0)
+    with pytest.raises(built.SdfkError, match="two-row coordinates"):
+        P(tree, xy=True, grid=(_ROWS, _LEN, 0))
+    # grids: whole rows from a row boundary on: row blocks (flat grids, n2 == 1: the flat build) ...
+    assert P(tree, grid=(_ROWS, _LEN, 0)) == (_AUTO, _ROWS_GRID, 0, 4)
+    assert P(tree, grid=(_ROWS, _LEN, 3 * _LEN), n=_N - 3 * _LEN) == (_AUTO, _ROWS_GRID, 0, 2)      # 14 rows: one block
+    assert P(tree, grid=(_LEN, 1, 0)) == (_AUTO, _ROWS2D_GRID, 0, 4)
+    # ... a start inside a row: line bricks, or plain
+    assert P(tree, grid=(_ROWS, _LEN, 5), n=_LEN) == (_AUTO, _TILE_GRID, 0, 0)
+    assert P(tree, grid=(_ROWS, _LEN, 5), n=_LEN, vec_ok=False) == (_AUTO, _PLAIN_GRID, 0, 0)
+    # chain mode: never line bricks, and row blocks of one grid plane each: 2 planes of 17 rows are 2 x 2 blocks, where any
+    # other program takes 34 consecutive rows as 3 blocks (unless SDFK_PLANE_BLOCKS=1 asks for planes, which other modules of
+    # this suite do: that half is asserted in a child process below); flags ignore the plane hint (their slot layout knows
+    # blocks of 16 consecutive rows only)
+    assert P(chain) == (_AUTO, _PLAIN_ARRAY, 0, 0)
+    assert P(chain, grid=(_ROWS, _LEN, 5), n=_LEN) == (_AUTO, _PLAIN_GRID, 0, 0)
+    assert P(chain, row_len=_LEN, flat=True) == (_AUTO, _ROWS2D_ARRAY, 0, 4)
+    assert P(chain, n=2 * _N, row_len=_LEN, plane_rows=_ROWS) == (_AUTO, _ROWS_ARRAY, 0, 8)
+    assert P(chain, n=2 * _N, row_len=_LEN, plane_rows=_ROWS, flags=True) == (_SPECIALIZED, _ROWS_ARRAY, 1, 6)
+    assert P(chain, n=2 * _N, row_len=_LEN, plane_rows=_ROWS, flat=True) == (_AUTO, _ROWS2D_ARRAY, 0, 6)
+    assert P(chain, n=2 * _N, grid=(_ROWS, _LEN, 0)) == (_AUTO, _ROWS_GRID, 0, 8)
+    assert P(chain, n=2 * _N, grid=(_ROWS, _LEN, 0), flags=True) == (_SPECIALIZED, _ROWS_GRID, 1, 6)
+    # a slab that starts 3 rows into a plane: 14 rows of the first plane (1 block), then a whole plane (2 blocks)
+    assert P(chain, n=31 * _LEN, row_len=_LEN, plane_rows=_ROWS, phase=3) == (_AUTO, _ROWS_ARRAY, 0, 6)
+    assert P(chain, n=31 * _LEN, grid=(_ROWS, _LEN, 3 * _LEN)) == (_AUTO, _ROWS_GRID, 0, 6)
+
+
+def test_fused_selection_sizes_its_scratch_for_the_planned_layout(built):
+    """The flag words of a fused selection are laid out from the evaluation's plan: 16 words per brick of a row-block plan
+    (whole blocks of 16 rows), else one word per 32 points and one more. sdfk_eval_select_scratch(n, row_len) holds either,
+    behind (tiles + 1) 8-byte offsets, tiles = words // 256 + 2, with 128 words of padding."""
+    bare, tree, _chain = _plan_programs(built)
+    scratch = built.lib().sdfk_eval_select_scratch
+
+    def size(words):
+        return (words // 256 + 2 + 1) * 8 + (words + 128) * 4
+    linear = (_N + 31) // 32 + 1
+    rows = _plan(built, tree, flags=True, row_len=_LEN)
+    assert rows[1] == _ROWS_ARRAY and 16 * rows[3] > linear
+    assert scratch(_N, _LEN) == size(16 * rows[3])                        # the tiled layout of the row-block plan
+    for prog, kw in ((tree, dict(row_len=0)), (tree, dict(row_len=_LEN, mode=_NOCULL)), (bare, dict(row_len=_LEN))):
+        assert _plan(built, prog, flags=True, **kw)[1:] == (_PLAIN_ARRAY, 1, 0)
+    assert scratch(_N, 0) == size(linear)                                 # the linear layout of the plain plan
+    assert scratch(_N, _LEN) >= scratch(_N, 0)                            # (one scratch serves whichever the plan picks)
+
+
+_LIMITS_SCRIPT = """
+import json, sys
+sys.path.insert(0, {root!r})
+sys.path.insert(0, {tests!r})
+from aegolius_amd import _engine
+import test_native_cpu as t
+bare, tree, chain = t._plan_programs(_engine)
+P = lambda prog, **kw: list(t._plan(_engine, prog, **kw))
+L = t._LEN
+print(json.dumps(dict(
+    rows=P(tree, row_len=L), rows_unaligned=P(tree, row_len=L, vec_ok=False), rows_flags=P(tree, row_len=L, flags=True),
+    rows_xy=P(tree, row_len=L, flat=True, xy=True), grid=P(tree, grid=(t._ROWS, L, 0)),
+    grid_unaligned=P(tree, grid=(t._ROWS, L, 0), vec_ok=False), grid_flags=P(tree, grid=(t._ROWS, L, 0), flags=True),
+    specialized=P(tree, row_len=L, mode=t._SPECIALIZED), chain=P(chain, row_len=L, flat=True), bare=P(bare, row_len=L),
+    no_hint=P(tree), planes=P(tree, n=2 * t._N, row_len=L, plane_rows=t._ROWS, mode=t._SPECIALIZED),
+    planes_grid=P(tree, n=2 * t._N, grid=(t._ROWS, L, 0), mode=t._SPECIALIZED),
+    planes_chain=P(chain, n=2 * t._N, row_len=L, plane_rows=t._ROWS))))
+"""
+
+
+def test_the_plan_of_programs_beyond_the_build_time_limits(built):
+    """SDFK_ROWS_LIMIT / SDFK_SPECIALIZE_LIMIT (instructions; both read once per process, hence the child processes): beyond
+    the first a program that is no chain gets line bricks instead of row blocks — plain where 16-byte accesses are not safe
+    or the coordinates have two rows, still row blocks when flags are asked for (the slot layout is theirs); beyond the
+    second AUTO stays on the interpreter kernel, unless the call has no interpreter form."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(**limits):
+        env = {k: v for k, v in os.environ.items() if k not in ("SDFK_ROWS_LIMIT", "SDFK_SPECIALIZE_LIMIT", "SDFK_PLANE_BLOCKS")}
+        env.update(limits)
+        res = subprocess.run([sys.executable, "-c", _LIMITS_SCRIPT.format(root=root, tests=os.path.join(root, "tests"))], env=env,
+                             capture_output=True, text=True, check=True)
+        return json.loads(res.stdout.strip().splitlines()[-1])
+    got = run(SDFK_ROWS_LIMIT="10")                               # the tree has 29 instructions
+    assert got["rows"] == [_AUTO, _TILE_ARRAY, 0, 0]
+    assert got["rows_unaligned"] == [_AUTO, _PLAIN_ARRAY, 0, 0]
+    assert got["rows_flags"] == [_SPECIALIZED, _ROWS_ARRAY, 1, 4]
+    assert got["rows_xy"] == [_SPECIALIZED, _PLAIN_ARRAY, 1, 0]
+    assert got["grid"] == [_AUTO, _TILE_GRID, 0, 0]
+    assert got["grid_unaligned"] == [_AUTO, _PLAIN_GRID, 0, 0]
+    assert got["grid_flags"] == [_SPECIALIZED, _ROWS_GRID, 1, 4]
+    assert got["specialized"] == [_SPECIALIZED, _TILE_ARRAY, 0, 0]
+    assert got["chain"] == [_AUTO, _ROWS2D_ARRAY, 0, 4]           # chains build in under a second whatever their size
+    assert got["no_hint"] == [_AUTO, _TILE_ARRAY, 0, 0]
+    got = run(SDFK_SPECIALIZE_LIMIT="10")
+    assert got["rows"][0] == got["grid"][0] == got["no_hint"][0] == _INTERPRET
+    assert got["specialized"] == [_SPECIALIZED, _ROWS_ARRAY, 0, 4]     # the caller asked for the kernel
+    assert got["rows_flags"] == [_SPECIALIZED, _ROWS_ARRAY, 1, 4]
+    assert got["rows_xy"] == [_SPECIALIZED, _ROWS2D_ARRAY, 1, 4]
+    assert got["chain"] == [_AUTO, _ROWS2D_ARRAY, 0, 4]
+    assert got["bare"] == [_AUTO, _PLAIN_ARRAY, 0, 0]             # (a sphere: below any limit that makes sense)
+    # the plane hint without SDFK_PLANE_BLOCKS: 34 rows in 2 planes are 3 blocks of consecutive rows, a chain's 2 x 2
+    assert got["planes"] == [_SPECIALIZED, _ROWS_ARRAY, 0, 6]
+    assert got["planes_grid"] == [_SPECIALIZED, _ROWS_GRID, 0, 6]
+    assert got["planes_chain"] == [_AUTO, _ROWS_ARRAY, 0, 8]
+
+
+# a switch for the generated source that no build survives: every kernel body declares floats
+REJECTING_DEFS = b"-Dfloat=void"
+
+
+def test_a_rejecting_define_fails_the_build_and_only_that_build(built):
+    """The extra -D switches are part of a code object's key: with one that hiprtc must reject the build fails, and with
+    the switches reset the same flavour builds — neither is ever served for the other."""
+    import aegolius_amd.cores as ns
+    from aegolius_amd._lower import lower_geometry
+    circle = ns.Circle(0.8)
+    circle.onion(0.1)
+    prog = built.Program.from_lowered(lower_geometry(circle))
+    flavour = built.FLAVOUR_PLAIN_ARRAY | built.FLAVOUR_XY
+    built.lib().sdfk_debug_set_rtc_defs(REJECTING_DEFS)
+    try:
+        with pytest.raises(built.SdfkError, match=r"\(-3\)"):
+            prog.compile_flavour(flavour)
+    finally:
+        built.lib().sdfk_debug_set_rtc_defs(b"")
+    assert prog.compile_flavour(flavour)[0] > 1000
+    built.lib().sdfk_debug_set_rtc_defs(REJECTING_DEFS)
+    try:
+        with pytest.raises(built.SdfkError, match=r"\(-3\)"):         # ... nor the good build for the broken one
+            prog.compile_flavour(flavour)
+    finally:
+        built.lib().sdfk_debug_set_rtc_defs(b"")
