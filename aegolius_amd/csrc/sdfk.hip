@@ -221,7 +221,7 @@ struct SpecModule {                   // a code object loaded on one device
     std::mutex mu;
     bool loaded = false, failed = false;
     hipModule_t mod = nullptr;
-    hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // ([2], [3]: the culled pair of the ray flavour)
+    hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};   // ([2], [3]: the culled pair of the ray / span flavours)
     std::string error;
 };
 

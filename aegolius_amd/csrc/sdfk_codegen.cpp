@@ -116,6 +116,44 @@ extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_raycam(
 }
 )SDFKW";
 
+// Spans (SDFK_FL_SPANS): the march of sdfk_trace_spans — every crossing and the chord — around the same field objects as
+// the ray flavour: the plain pair, and for long chains the pair that carries SdfkCullField and its per-wave lists.
+static const char kSpans[] = R"SDFKW(
+extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_spans(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkRaysArray src, sdfk_rayopts opts, int max_crossings,
+    float* __restrict__ out_chord, int* __restrict__ out_count, unsigned char* __restrict__ out_status,
+    int* __restrict__ out_steps, float* __restrict__ out_cross, long long cstride) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
+}
+extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_spancam(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, sdfk_camera cam, sdfk_rayopts opts, int max_crossings,
+    float* __restrict__ out_chord, int* __restrict__ out_count, unsigned char* __restrict__ out_status,
+    int* __restrict__ out_steps, float* __restrict__ out_cross, long long cstride) {
+    const SdfkSpecField field = {PRM, TAB};
+    const SdfkRaysCamera src = {cam};
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
+}
+)SDFKW";
+static const char kSpansCullKernels[] = R"SDFKW(extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_spans_cull(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkRaysArray src, sdfk_rayopts opts, int max_crossings,
+    float* __restrict__ out_chord, int* __restrict__ out_count, unsigned char* __restrict__ out_status,
+    int* __restrict__ out_steps, float* __restrict__ out_cross, long long cstride) {
+    __shared__ sdfk_raylists lists[SDFK_RAY_BLOCK / 64];
+    const SdfkCullField field = {PRM, TAB, &lists[sdfk_tx() >> 6], nullptr, (int)(sdfk_tx() & 63u), {0.0f, 0.0f, 0.0f}, -1.0f, 0u, 0u};
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
+}
+extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_spancam_cull(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, sdfk_camera cam, sdfk_rayopts opts, int max_crossings,
+    float* __restrict__ out_chord, int* __restrict__ out_count, unsigned char* __restrict__ out_status,
+    int* __restrict__ out_steps, float* __restrict__ out_cross, long long cstride) {
+    __shared__ sdfk_raylists lists[SDFK_RAY_BLOCK / 64];
+    const SdfkCullField field = {PRM, TAB, &lists[sdfk_tx() >> 6], nullptr, (int)(sdfk_tx() & 63u), {0.0f, 0.0f, 0.0f}, -1.0f, 0u, 0u};
+    const SdfkRaysCamera src = {cam};
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
+}
+)SDFKW";
+
 // Sub-voxel occupancy (SDFK_FL_OCCUPANCY): the sample pass of sdfk_occdev.h around the same field object as the plain ray
 // kernels, over a list of cells or over all cells of a slab; the same text as the interpreter sample kernel
 // (sdfk_occupancy.inc) but for the evaluator.
@@ -347,7 +385,10 @@ struct SdfkCullField {
         return sdfk_chain_tail<float>(acc, C_0, PRM, TAB);
     }
 };
-extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_rays_cull(
+)SDFKW";
+// (the kernels apart from the field object, which the span flavour wraps as well: the two pieces in a row are the text
+//  the ray flavour always had)
+static const char kRaysCullKernels[] = R"SDFKW(extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spec_rays_cull(
     const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkRaysArray src, sdfk_rayopts opts,
     float* __restrict__ out_t, unsigned char* __restrict__ out_status, int* __restrict__ out_steps,
     float* __restrict__ out_n, long long nstride, unsigned long long* STATS) {
@@ -2764,7 +2805,7 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
     g.s += "\n";
     g.s += kEmbeddedAccess;
     char buf[64];
-    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY) {
+    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY || flavour == SDFK_FL_SPANS) {
         // Sphere tracing: the plain body, one ray per lane (scalar T: lanes diverge per ray, and two rays per lane would
         // double every wave's tail), inside the marching loop of sdfk_raydev.h. A long hard union that the field kernels
         // run table-driven ("chain mode") keeps its table-driven plain body, which builds in a second whatever the number
@@ -2795,12 +2836,13 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
         }
         g.s += kEmbeddedRaydev;
         g.s += kSpecField;
-        g.s += kRays;
+        g.s += flavour == SDFK_FL_SPANS ? kSpans : kRays;     // (the span flavour: the same field objects, the other march)
         if (chain) {
             g.s += "\n#ifndef SDFK_RAYS_CULL_MIN_LEAVES\n#define SDFK_RAYS_CULL_MIN_LEAVES 64    // (measured: DESIGN 4.14 has the table)\n#endif\n"
                    "#if SDFK_NLEAF >= SDFK_RAYS_CULL_MIN_LEAVES\n";
             g.s += kWaveHelpers;
             g.s += kRaysCull;
+            g.s += flavour == SDFK_FL_SPANS ? kSpansCullKernels : kRaysCullKernels;
             g.s += "#endif\n";
         }
         return g.s;

@@ -404,7 +404,7 @@ static const char* const kFlavourFn[SDFK_FL_COUNT][2] = {
     {"sdfk_spec_v4", "sdfk_spec_v1"}, {"sdfk_spec_g4", "sdfk_spec_g1"}, {"sdfk_spec_t", nullptr}, {"sdfk_spec_tg", nullptr},
     {"sdfk_spec_tmask", nullptr},     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr}, {"sdfk_spec_rmask", nullptr},
     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr},        {"sdfk_spec_rays", "sdfk_spec_raycam"},
-    {"sdfk_spec_occ_list", "sdfk_spec_occ_all"}};
+    {"sdfk_spec_occ_list", "sdfk_spec_occ_all"},                        {"sdfk_spec_spans", "sdfk_spec_spancam"}};
 
 // hiprtc is entered by ONE thread at a time, and never while a code object is being loaded (hipModuleLoadData):
 // g_rtc_mu. Background builds are queued to one worker thread, which is drained before the interpreter / the
@@ -551,6 +551,7 @@ extern "C" int sdfk_program_compile_check(sdfk_program* p, size_t* code_size) {
     for (int f = 0; f < SDFK_FL_COUNT; ++f) {
         if (f == SDFK_FL_RAYS) continue;                        // (not an evaluation flavour: built by the first ray cast)
         if (f == SDFK_FL_OCCUPANCY) continue;                   // (nor this one: built by the first occupancy call)
+        if (f == SDFK_FL_SPANS) continue;                       // (nor this one: built by the first span call)
         if (p->sites.empty() && f != SDFK_FL_PLAIN_ARRAY && f != SDFK_FL_PLAIN_GRID) continue;
         if (p->chain_mode && (f == SDFK_FL_TILE_ARRAY || f == SDFK_FL_TILE_GRID || f == SDFK_FL_TILE_MASK || f == SDFK_FL_ROWS_MASK)) continue;
         std::shared_ptr<CodeObject> e = code_get(flavour_key(p, f, rwb), [&] { return flavour_source(p, f); }, rwb, true);
@@ -569,12 +570,14 @@ extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t
     if (flavour >= 0) flavour &= ~(SDFK_FLAVOUR_FLAGS | SDFK_FLAVOUR_XY);
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_program_compile_flavour: unknown flavour");
     if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY)
+        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_SPANS)
         return fail(-2, "sdfk_program_compile_flavour: the program has no cull sites");
     if (with_flags && flavour == SDFK_FL_RAYS)
         return fail(-2, "sdfk_program_compile_flavour: the ray flavour has no flag-writing or two-row build");
     if (with_flags && flavour == SDFK_FL_OCCUPANCY)
         return fail(-2, "sdfk_program_compile_flavour: the occupancy flavour has no flag-writing or two-row build");
+    if (with_flags && flavour == SDFK_FL_SPANS)
+        return fail(-2, "sdfk_program_compile_flavour: the span flavour has no flag-writing or two-row build");
     if ((with_flags & 2) && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_ROWS2D_ARRAY)
         return fail(-2, "sdfk_program_compile_flavour: two-row coordinates exist for the plain and the flat row-block array kernels");
     if ((with_flags & 1) && (flavour == SDFK_FL_TILE_ARRAY || flavour == SDFK_FL_TILE_GRID || flavour == SDFK_FL_TILE_MASK ||
@@ -595,7 +598,7 @@ extern "C" int sdfk_debug_compile_external(sdfk_program* p, int flavour, size_t*
     if (!p) return fail(-1, "null program");
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_debug_compile_external: unknown flavour");
     if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY)
+        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_SPANS)
         return fail(-2, "sdfk_debug_compile_external: the program has no cull sites");
     if (!rtc_helper_available()) return fail(-9, "sdfk_rtc_helper is not next to libsdfk.so (or hiprtc cannot be located)");
     std::vector<char> co;
@@ -664,6 +667,13 @@ static std::shared_ptr<SpecModule> get_module(sdfk_program* p, int device, int f
             // long chains come with a second pair of kernels that cull along the rays (sdfk_codegen.cpp: kRaysCull)
             if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_rays_cull") != hipSuccess ||
                 hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_raycam_cull") != hipSuccess) {
+                m->fn[2] = m->fn[3] = nullptr;
+                (void)hipGetLastError();
+            }
+        }
+        if (he == hipSuccess && flavour == SDFK_FL_SPANS) {     // (likewise: SdfkCullField inside the span march)
+            if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_spans_cull") != hipSuccess ||
+                hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_spancam_cull") != hipSuccess) {
                 m->fn[2] = m->fn[3] = nullptr;
                 (void)hipGetLastError();
             }

@@ -168,4 +168,96 @@ static __device__ __forceinline__ void sdfk_trace(const SRC& src, const FIELD& f
     }
 }
 
+// ---- spans: the march that goes on through the surface ---------------------------------------------------------------------
+// Every entry and exit crossing of a ray with the solid { f <= 0 }, and the length of the ray inside it (the chord). The
+// rule (aegolius_amd/render.py states it for users; tests/spans_reference.py is its float64 copy), per ray, in fp32:
+//     t = t_min; count = 0; chord = 0
+//     repeat at most max_steps times (evaluation index e = 0, 1, ...):
+//         f      = field(o + t d)                              fmaf(t, d, o) per component, as above
+//         inside = (f <= 0)
+//         if e == 0: was = inside; inside0 = inside; t_in = t_min          starting inside is not a crossing
+//         else if inside != was:                                          a sign change between t_prev and t
+//             tc = fmaf(t - t_prev, |f_prev| / (|f_prev| + |f|), t_prev)      secant; the denominator is > 0
+//             if count < K: crossings[count] = tc
+//             count += 1
+//             if inside: t_in = tc   else: chord += tc - t_in
+//             was = inside
+//         thr    = max(eps, cone t)
+//         t_prev = t; f_prev = f
+//         t_next = t + max(|f| * (1 / L), thr)                 1 / L rounded once on the host; steps += 1
+//         if not (t_next > t): status = LIMIT; stop            no progress in fp32: never loop in place
+//         t = t_next
+//         if t > t_max: if was: chord += t_max - t_in;  status = COMPLETE; stop
+//     otherwise: status = LIMIT
+//     on LIMIT, either way: if was: chord += t_prev - t_in     (t_prev: the last evaluated parameter)
+// A step of |f| / L cannot cross the surface, so the sign changes only inside floor steps of length thr: the state at every
+// evaluated point is the field's own, every crossing is bracketed within thr, and only features thinner than thr along
+// the ray can be missed, as a pair. The loop has the wave-uniform shape of sdfk_trace: it runs while any lane marches, calls
+// the hook before every evaluation, and finished lanes evaluate along, masked out of every update (e is the trip count,
+// the same number on every lane). A crossing is stored when it is found — row k of ray i at k * cstride + i, one
+// contiguous line per wave — so that no lane keeps an indexed array; rows from `count` on are not written.
+#define SDFK_SPAN_COMPLETE 0u
+#define SDFK_SPAN_LIMIT 2u
+#define SDFK_SPAN_INSIDE0 4u       // added to the status of a ray that is inside the solid at t_min
+#define SDFK_SPAN_MAX_CROSSINGS 32
+
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_trace_spans(const SRC& src, const FIELD& field, const sdfk_rayopts R,
+                                                        const int max_crossings, float* __restrict__ out_chord,
+                                                        int* __restrict__ out_count, unsigned char* __restrict__ out_status,
+                                                        int* __restrict__ out_steps, float* __restrict__ out_cross,
+                                                        long long cstride) {
+    V3 o, d;
+    long long at;
+    const bool live = sdfk_ray_load(src, o, d, at);
+    float t = R.t_min, t_prev = R.t_min, f_prev = 0.0f, t_in = R.t_min, chord = 0.0f;
+    unsigned status = SDFK_SPAN_LIMIT;
+    int steps = 0, count = 0;
+    bool was = false, inside0 = false;
+    bool marching = live;
+    for (int it = 0; it < R.max_steps; ++it) {
+        if (!__any(marching)) break;
+        const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
+        field.prepare(p, t, marching, 0.0f);
+        const float f = field(p);
+        if (marching) {
+            const bool inside = f <= 0.0f;
+            if (it == 0) {
+                was = inside;
+                inside0 = inside;
+            } else if (inside != was) {
+                const float af = fabsf(f_prev);
+                const float tc = fmaf(t - t_prev, af / (af + fabsf(f)), t_prev);
+                if (count < max_crossings) out_cross[(long long)count * cstride + at] = tc;
+                ++count;
+                if (inside) t_in = tc;
+                else chord += tc - t_in;
+                was = inside;
+            }
+            const float thr = fmaxf(R.eps, R.cone * t);
+            t_prev = t;
+            f_prev = f;
+            const float t_next = t + fmaxf(fabsf(f) * R.inv_lip, thr);
+            ++steps;
+            if (!(t_next > t)) {
+                marching = false;                               // (status stays LIMIT)
+            } else {
+                t = t_next;
+                if (t > R.t_max) {
+                    if (was) chord += R.t_max - t_in;
+                    status = SDFK_SPAN_COMPLETE;
+                    marching = false;
+                }
+            }
+        }
+    }
+    if (live) {
+        if (status == SDFK_SPAN_LIMIT && was) chord += t_prev - t_in;
+        out_chord[at] = chord;
+        out_count[at] = count;
+        out_status[at] = (unsigned char)(status | (inside0 ? SDFK_SPAN_INSIDE0 : 0u));
+        out_steps[at] = steps;
+    }
+}
+
 #endif  // SDFK_RAYDEV_H

@@ -11,6 +11,8 @@
 //   * the specialised flavour (SDFK_FL_RAYS, sdfk_codegen.cpp) wraps the generated sdfk_point<float> in the same loop;
 //     long hard unions (chain mode) get a second pair of kernels there that folds the chain over per-wave survivor
 //     lists in LDS (kRaysCull) — what SPECIALIZED / AUTO launch, NOCULL the plain pair; same bits.
+//   * sdfk_spans_interp_kernel / SDFK_FL_SPANS: the same field objects inside sdfk_trace_spans, the march that goes on
+//     through the surface (every crossing, the chord); selected, culled and served by the interpreter exactly as above.
 // Outputs per ray: t (fp32), status (1 byte: 0 miss, 1 hit, 2 step limit), steps (int32), optionally the stencil normal
 // (three strided rows). Plain vector stores, written once; no atomics, no LDS.
 #include "sdfk_raydev.h"
@@ -75,6 +77,20 @@ __global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_rays_interp_kernel(const 
                                                                          float* __restrict__ out_n, long long nstride) {
     const SdfkInterpField<NC, NV> field = {code, n_instr, prm, tab, result_reg};
     sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride);
+}
+
+// The span march (sdfk_trace_spans) around the same field object: every crossing and the chord instead of the first hit.
+template <int NC, int NV, typename SRC>
+__global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spans_interp_kernel(const uint2* __restrict__ code, int n_instr,
+                                                                          const float* __restrict__ prm,
+                                                                          const float* __restrict__ tab, int result_reg,
+                                                                          SRC src, sdfk_rayopts opts, int max_crossings,
+                                                                          float* __restrict__ out_chord, int* __restrict__ out_count,
+                                                                          unsigned char* __restrict__ out_status,
+                                                                          int* __restrict__ out_steps,
+                                                                          float* __restrict__ out_cross, long long cstride) {
+    const SdfkInterpField<NC, NV> field = {code, n_instr, prm, tab, result_reg};
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
 }
 
 // ---- host side ----------------------------------------------------------------------------------
@@ -251,4 +267,102 @@ extern "C" int sdfk_trace_camera_device(sdfk_program* p, const float* camera, in
     c.width = width, c.height = height, c.ortho = orthographic ? 1 : 0;
     return rays_run("sdfk_trace_camera_device", p, nullptr, &c, (long long)width * height, o, d_t, d_status, d_steps,
                     d_normals, (long long)normal_stride, stream, mode);
+}
+
+// ---- spans: every crossing and the chord (sdfk_trace_spans) --------------------------------------------------------------
+// array rays (cam == nullptr) or camera rays, as rays_run; the kernel follows pick_kernel exactly as there
+static int spans_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, const sdfk_camera* cam, long long count,
+                     const sdfk_rayopts& opts, float* d_chord, int* d_count, unsigned char* d_status, int* d_steps,
+                     float* d_cross, long long cstride, int max_crossings, void* stream_, int mode) {
+    const std::string w = who;
+    if (!d_chord || !d_count || !d_status || !d_steps) return fail(-1, w + ": null output pointer");
+    if (max_crossings < 0 || max_crossings > SDFK_SPAN_MAX_CROSSINGS)
+        return fail(-1, w + ": max_crossings from 0 to " + std::to_string(SDFK_SPAN_MAX_CROSSINGS));
+    if (d_cross && max_crossings > 0 && cstride < count) return fail(-1, w + ": crossing row stride smaller than the ray count");
+    int K = d_cross ? max_crossings : 0;                       // (no array: the crossings are counted and not stored)
+    int bad = -1;
+    const int chk = sdfk_program_rays_check(p, &bad);
+    if (chk) return fail(chk < 0 ? chk : -3, w + ": " + g_err);
+    if (count == 0) return 0;
+    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
+    LaunchCtx x;
+    int rc = launch_ctx(p, stream_, &x);
+    if (rc) return rc;
+    hipStream_t stream = x.stream;
+    unsigned blocks;
+    if (cam) {
+        const long long tiles = (long long)((cam->width + 7) / 8) * ((cam->height + 7) / 8);
+        blocks = (unsigned)((tiles + SDFK_RAY_BLOCK / 64 - 1) / (SDFK_RAY_BLOCK / 64));
+    } else {
+        blocks = (unsigned)((count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
+    }
+    std::shared_ptr<SpecModule> sk;                            // (a failed build falls back in AUTO only)
+    rc = pick_kernel(p, x.device, SDFK_FL_SPANS, 0, mode, mode == SDFK_MODE_AUTO, "span kernel", false, &sk);
+    if (rc) return rc;
+    const float* prm = x.prm;
+    const float* tab = x.tab;
+    sdfk_rayopts o = opts;
+    if (sk) {
+        const bool cull = mode != SDFK_MODE_NOCULL && sk->fn[2] && sk->fn[3];   // the culled pair: long chains only
+        sdfk_camera c;
+        SdfkRaysArray a;
+        void* src = cam ? (void*)&c : (void*)&a;
+        if (cam) c = *cam;
+        else a = *arr;
+        void* args[] = {&prm, &tab, src, &o, &K, &d_chord, &d_count, &d_status, &d_steps, &d_cross, &cstride};
+        HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (cam ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
+                                     nullptr));
+        return 0;
+    }
+    auto launch = [&](auto src) {
+        using SRC = decltype(src);
+#define SDFK_SPANS_GO(NC, NV) hipLaunchKernelGGL((sdfk_spans_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream, \
+                                                 x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, o, K, d_chord, d_count, d_status, d_steps, d_cross, cstride)
+        SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_SPANS_GO);
+#undef SDFK_SPANS_GO
+    };
+    if (cam) launch(SdfkRaysCamera{*cam});
+    else launch(*arr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sdfk_span_rays_device(sdfk_program* p, const float* d_origins, int64_t origin_stride, const float* d_directions,
+                                     int64_t direction_stride, int64_t n, float t_min, float t_max, float eps, float cone,
+                                     float inv_lipschitz, int max_steps, float* d_chord, int* d_count, unsigned char* d_status,
+                                     int* d_steps, float* d_crossings, int64_t crossing_stride, int max_crossings, void* stream,
+                                     int mode) {
+    if (!p) return fail(-1, "null program");
+    if (n < 0) return fail(-1, "sdfk_span_rays_device: negative ray count");
+    if (n > 0 && (!d_origins || !d_directions)) return fail(-1, "sdfk_span_rays_device: null ray pointer");
+    if (origin_stride < n || direction_stride < n)
+        return fail(-1, "sdfk_span_rays_device: row stride smaller than the ray count");
+    sdfk_rayopts o;
+    int rc = rays_options("sdfk_span_rays_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
+    if (rc) return rc;
+    SdfkRaysArray a = {d_origins, (long long)origin_stride, d_directions, (long long)direction_stride, (long long)n};
+    return spans_run("sdfk_span_rays_device", p, &a, nullptr, n, o, d_chord, d_count, d_status, d_steps, d_crossings,
+                     (long long)crossing_stride, max_crossings, stream, mode);
+}
+
+extern "C" int sdfk_span_camera_device(sdfk_program* p, const float* camera, int width, int height, int orthographic,
+                                       float t_min, float t_max, float eps, float cone, float inv_lipschitz, int max_steps,
+                                       float* d_chord, int* d_count, unsigned char* d_status, int* d_steps, float* d_crossings,
+                                       int64_t crossing_stride, int max_crossings, void* stream, int mode) {
+    if (!p) return fail(-1, "null program");
+    if (!camera) return fail(-1, "sdfk_span_camera_device: null camera");
+    if (width < 0 || height < 0 || width > 32768 || height > 32768)
+        return fail(-1, "sdfk_span_camera_device: image sizes from 0 to 32768");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(camera[i])) return fail(-1, "sdfk_span_camera_device: the camera record is not finite");
+    sdfk_rayopts o;
+    int rc = rays_options("sdfk_span_camera_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
+    if (rc) return rc;
+    sdfk_camera c;
+    for (int i = 0; i < 3; ++i) c.eye[i] = camera[i], c.fwd[i] = camera[3 + i], c.du[i] = camera[6 + i], c.dv[i] = camera[9 + i];
+    c.inv_w = width ? 1.0f / (float)width : 0.0f;
+    c.inv_h = height ? 1.0f / (float)height : 0.0f;
+    c.width = width, c.height = height, c.ortho = orthographic ? 1 : 0;
+    return spans_run("sdfk_span_camera_device", p, nullptr, &c, (long long)width * height, o, d_chord, d_count, d_status,
+                     d_steps, d_crossings, (long long)crossing_stride, max_crossings, stream, mode);
 }

@@ -1,10 +1,13 @@
-"""Sphere tracing of geometries on the GPU: ray casts and depth / normal images (kernels: csrc/sdfk_rays.inc).
+"""Sphere tracing of geometries on the GPU: ray casts, depth / normal images, and spans — every crossing of a ray with
+the solid, chords and thickness images (kernels: csrc/sdfk_rays.inc).
 
     from aegolius_amd import render
     cam = render.Camera(eye=(2.2, 1.6, 1.9), target=(0, 0, 0), fov=40)
     img = render.render(geometry, cam, 1920, 1080, t_min=0.0, t_max=8.0)
     img.save_pgm("part.pgm", img.shade(light=(1, 1, 2)))
     hits = render.cast(geometry, origins, directions, t_max=8.0)          # arbitrary rays, (3, N) arrays
+    sp = render.spans(geometry, origins, directions, t_max=8.0)           # every crossing, the chord, parity
+    xray = render.thickness(geometry, cam, 1920, 1080, t_max=8.0)         # chord per pixel: a radiograph
 
 No field and no grid are made: the geometry's program (create()'s own) is evaluated along every ray.
 
@@ -42,6 +45,39 @@ the kernel the record {eye, fwd, du, dv} in float32 and the kernel generates the
 `Camera.rays` is the same formula on the host in float64. The hit threshold is the pixel's footprint: `cone` defaults
 to tan(fov / 2) / H, half the angular size of a pixel (orthographic: `eps` defaults to height / (2 H), half a pixel).
 
+Spans: what lies behind the first surface. `spans` (arbitrary rays) and `thickness` (camera rays) march on through the
+solid { f <= 0 } and report every entry and exit crossing and the length of the ray inside it, the chord (one definition:
+the kernels, tests/spans_reference.py and this text), per ray, in float32:
+
+    t = t_min; count = 0; chord = 0
+    repeat at most max_steps times (evaluation index e = 0, 1, ...):
+        f      = field(o + t d)                       # fmaf(t, d, o) per component
+        inside = (f <= 0)
+        if e == 0:  was = inside; inside0 = inside; t_in = t_min       # starting inside is not a crossing
+        else if inside != was:                                        # a sign change between t_prev and t
+            tc = fmaf(t - t_prev, |f_prev| / (|f_prev| + |f|), t_prev)   # secant; the denominator is > 0
+            if count < K: crossings[count] = tc
+            count += 1
+            if inside: t_in = tc   else: chord += tc - t_in
+            was = inside
+        thr    = max(eps, cone * t)
+        t_prev = t; f_prev = f
+        t_next = t + max(|f| * (1/L), thr)            # float32(1 / L); steps += 1
+        if not (t_next > t): status = LIMIT; stop     # no progress in float32: never loop in place
+        t = t_next
+        if t > t_max: if was: chord += t_max - t_in;  status = COMPLETE; stop
+    otherwise: status = LIMIT
+    on LIMIT, either way: if was: chord += t_prev - t_in              # t_prev: the last evaluated parameter
+
+With a valid bound L a step of |f| / L cannot cross the surface, so the sign changes only inside floor steps of length
+thr: the inside / outside state at every evaluated point is the field's own, every recorded crossing is bracketed within
+thr, and only features thinner than thr along the ray can be missed, and then as a pair of crossings. `eps` must be
+positive and at least 2^-20 max(|t_min|, |t_max|), so that a floor step always advances t in float32. `count` counts all
+crossings, `crossings` keeps the first K = max_crossings (0 to 32) of them; `steps` counts the evaluations. Parity gives
+point-in-solid (`inside0`, or count odd for a ray from outside), the chord is the optical path length through the part,
+`intervals` the wall thicknesses along a ray, and `ThicknessImage.volume()` of an orthographic image the ray-integrated
+volume to put next to `enclosure.volume_bounds`. Refusals and `lipschitz=` are those of `cast`.
+
 Long hard unions and intersections (from 64 members on, among the trees the field kernels run "in chain mode") are culled along
 the rays. The 64 rays of a wave — an 8 x 8 pixel tile in `render`, 64 consecutive rays in `cast` — bound the points they
 are about to evaluate by a sphere, every member is evaluated once at its centre, and only the members that can be the
@@ -62,6 +98,10 @@ from ._lower import OWNED, NeedsStage, _deep
 from .autodiff import UnsupportedOpError, _TracingLowerer      # (autodiff.py marks the lowerer as used from here)
 
 MISS, HIT, LIMIT = 0, 1, 2
+COMPLETE = 0                                  # spans / thickness: the ray was followed to t_max (LIMIT = 2 as above)
+_INSIDE0 = 4                                  # the kernels' status byte carries inside0 as this bit
+MAX_CROSSINGS = 32                            # csrc/sdfk_raydev.h SDFK_SPAN_MAX_CROSSINGS
+SPAN_EPS_FLOOR = 2.0 ** -20                   # eps >= this * max(|t_min|, |t_max|): t + eps > t in float32 on the whole ray
 STENCIL_FLOOR = np.float32(2.0 ** -16)        # csrc/sdfk_raydev.h sdfk_ray_stencil_width
 
 
@@ -124,6 +164,18 @@ def _options(t_min, t_max, eps, cone, max_steps):
     if not (np.isfinite(eps) and eps >= 0.0 and np.isfinite(cone) and cone >= 0.0):
         raise ValueError("eps and cone must be finite and not negative")
     return tuple(float(np.float32(x)) for x in (t_min, t_max, eps, cone)) + (int(max_steps),)   # as the kernel sees them
+
+
+def _span_options(t_min, t_max, eps, cone, max_steps, max_crossings):
+    t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
+    floor = SPAN_EPS_FLOOR * max(abs(t_min), abs(t_max))
+    if not (eps > 0.0 and eps >= floor):
+        raise ValueError("eps must be positive and at least 2^-20 max(|t_min|, |t_max|) = %.3g, so that a floor step always "
+                         "advances t in float32; got %g" % (floor, eps))
+    k = int(max_crossings)
+    if not 0 <= k <= MAX_CROSSINGS:
+        raise ValueError("max_crossings from 0 to %d; got %r" % (MAX_CROSSINGS, max_crossings))
+    return t_min, t_max, eps, cone, max_steps, k
 
 
 def _program(low):
@@ -323,6 +375,86 @@ class Image:
         np.savez_compressed(path, **arrays)
 
 
+def _intervals(crossings, count, inside0, status, chord, t_min, t_max):
+    """The (t_enter, t_exit) pairs of one ray from its stored crossings (float64)."""
+    n = int(count)
+    if n > len(crossings):
+        raise ValueError("the ray has %d crossings and %d are stored: raise max_crossings" % (n, len(crossings)))
+    ts = [float(x) for x in crossings[:n]]
+    if inside0:
+        ts.insert(0, float(t_min))
+    if len(ts) % 2:                                             # still inside where the march ended
+        closed = sum(b - a for a, b in zip(ts[0:-1:2], ts[1::2]))
+        # COMPLETE: the ray was followed to t_max. LIMIT: to the last evaluated t, which the chord was closed with
+        ts.append(float(t_max) if status == COMPLETE else ts[-1] + max(float(chord) - closed, 0.0))
+    return list(zip(ts[0::2], ts[1::2]))
+
+
+class RaySpans:
+    """Result of spans(): chord (N,) float32 — the length of the ray inside the solid —, count (N,) int32 (all crossings,
+    also those beyond K), inside0 (N,) bool (inside at t_min), status (N,) uint8 (COMPLETE 0: followed to t_max, LIMIT 2:
+    max_steps reached, or no progress in float32), steps (N,) int32 (evaluations made), crossings (K, N) float32 (the
+    first K crossing parameters in order, NaN past count), truncated (N,) bool (count > K). With resident=True, chord is a
+    DeviceField and crossings a DeviceRows (None for K = 0); the small arrays are host arrays."""
+
+    def __init__(self, chord, count, status, steps, crossings, t_min, t_max, max_crossings):
+        status = np.asarray(status, dtype=np.uint8)
+        self.chord, self.count, self.steps, self.crossings = chord, count, steps, crossings
+        self.inside0 = (status & _INSIDE0) != 0
+        self.status = status & np.uint8(3)
+        self.t_min, self.t_max, self.max_crossings = float(t_min), float(t_max), int(max_crossings)
+        self.truncated = np.asarray(count) > self.max_crossings
+
+    def __repr__(self):
+        return "RaySpans(%d rays, %d crossings, %d at the step limit)" % (self.status.size, int(np.sum(self.count, dtype=np.int64)),
+                                                                          int(np.count_nonzero(self.status == LIMIT)))
+
+    def intervals(self, i):
+        """The (t_enter, t_exit) pairs of ray i, in order. The first opens at t_min when inside0; a ray that is still
+        inside where it ended closes at t_max, or on LIMIT at the last evaluated t. ValueError if the ray is truncated."""
+        def host(x):
+            return x.numpy() if isinstance(x, _engine.DeviceField) else x.download_rows() if isinstance(x, _engine.DeviceRows) else x
+        cr = np.zeros((0, self.status.size), dtype=np.float32) if self.crossings is None else host(self.crossings)
+        return _intervals(cr[:, i], self.count[i], self.inside0[i], self.status[i], host(self.chord)[i], self.t_min, self.t_max)
+
+
+class ThicknessImage:
+    """Result of thickness(): chord (H, W) float32, count (H, W) int32, inside0 (H, W) bool, status (H, W) uint8
+    (COMPLETE / LIMIT), steps (H, W) int32, crossings (K, H, W) float32 (NaN past count) or None for K = 0, and the camera,
+    eps, cone, t_min and t_max it was made with."""
+
+    def __init__(self, chord, count, status, steps, crossings, camera=None, eps=0.0, cone=0.0, t_min=0.0, t_max=0.0):
+        status = np.asarray(status, dtype=np.uint8)
+        self.chord, self.count, self.steps, self.crossings = chord, count, steps, crossings
+        self.inside0 = (status & _INSIDE0) != 0
+        self.status = status & np.uint8(3)
+        self.camera, self.eps, self.cone, self.t_min, self.t_max = camera, eps, cone, t_min, t_max
+
+    def __repr__(self):
+        h, w = self.status.shape
+        return "ThicknessImage(%d x %d, largest chord %g)" % (w, h, float(np.max(self.chord)) if self.chord.size else 0.0)
+
+    def volume(self):
+        """Sum of chord x pixel area in float64: the midpoint rule over the image plane of an ORTHOGRAPHIC camera, whose
+        rays are parallel — the volume of the solid between t_min and t_max inside the image's prism."""
+        if self.camera is None or not self.camera.ortho:
+            raise ValueError("volume() is the sum of chord x pixel area over parallel rays: it needs an orthographic camera")
+        h, w = self.status.shape
+        side = self.camera.height / h                           # square pixels: the image is height W / H wide
+        return float(np.sum(self.chord, dtype=np.float64) * side * side)
+
+    def save_pgm(self, path, scale=None):
+        """Binary PGM (P5) radiograph: chord / scale, clipped to [0, 1] (default scale: the largest chord), 0 = empty."""
+        top = float(np.max(self.chord)) if scale is None else float(scale)
+        Image._pnm(path, np.asarray(self.chord, dtype=np.float64) / top if top > 0.0 else np.zeros(self.chord.shape), "P5", 1)
+
+    def save_npz(self, path):
+        arrays = {"chord": self.chord, "count": self.count, "inside0": self.inside0, "status": self.status, "steps": self.steps}
+        if self.crossings is not None:
+            arrays["crossings"] = self.crossings
+        np.savez_compressed(path, **arrays)
+
+
 # ---- device plumbing ----------------------------------------------------------------------------------------------------
 def _outputs(fields, scratch, n, normals):
     """The trace kernels' outputs, entered on two ExitStacks: t (DeviceField) and the normals (DeviceVectorField or
@@ -344,6 +476,54 @@ def _normal_args(nrm):
     return _engine._vp(nrm.ptr), nrm.stride
 
 
+def _span_outputs(fields, scratch, n, k):
+    """The span kernels' outputs: the chord (DeviceField) and the (k, n) crossings (DeviceRows filled with NaN, None for
+    k = 0) on `fields`; count, status and steps (DeviceBuffers) on `scratch`."""
+    chord = fields.enter_context(_engine.DeviceField(n, config.device))
+    cross = None
+    if k:
+        cross = fields.enter_context(_engine.DeviceRows(k, n, config.device, what="render"))
+        # rows past a ray's count are never written: NaN everywhere first. One row crosses PCIe, the others are copies of
+        # what is already there, doubling.
+        cross.upload(np.full(cross.stride, np.nan, dtype=np.float32))
+        done = 1
+        while done < k:
+            rows = min(done, k - done)
+            cross.copy_from(cross.ptr, cross.offset(rows), cross.offset(done))
+            done += rows
+    d_count = scratch.enter_context(_engine.DeviceBuffer(max(n, 16) * 4, what="render"))
+    d_status = scratch.enter_context(_engine.DeviceBuffer(max(n, 64), what="render"))
+    d_steps = scratch.enter_context(_engine.DeviceBuffer(max(n, 16) * 4, what="render"))
+    return chord, cross, d_count, d_status, d_steps
+
+
+def _cross_args(cross):
+    if cross is None:
+        return None, 0
+    return cross.at(), cross.stride
+
+
+def _check_rays(origins, directions):
+    """The checks of cast() on a pair of ray arrays -> the number of rays."""
+    for name, x in (("origins", origins), ("directions", directions)):
+        if not isinstance(x, _engine.DeviceVectorField):
+            shape = np.shape(x)
+            if len(shape) != 2 or shape[0] != 3:
+                raise ValueError("%s must have shape (3, N); got %r" % (name, shape))
+    if not isinstance(directions, _engine.DeviceVectorField):
+        d32 = np.asarray(directions, dtype=np.float32).astype(np.float64)
+        len2 = (d32 * d32).sum(axis=0)
+        bad = ~(np.abs(len2 - 1.0) <= 1e-5)
+        if bad.any():
+            raise ValueError("directions must be unit vectors: ray %d has |d|^2 = %.9g" %
+                             (int(np.argmax(bad)), float(len2[np.argmax(bad)])))
+    n_o = origins.n if isinstance(origins, _engine.DeviceVectorField) else int(np.shape(origins)[1])
+    n_d = directions.n if isinstance(directions, _engine.DeviceVectorField) else int(np.shape(directions)[1])
+    if n_o != n_d:
+        raise ValueError("%d origins for %d directions" % (n_o, n_d))
+    return n_o
+
+
 # ---- public interface ---------------------------------------------------------------------------------------------------
 def cast(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0.0, max_steps=256, lipschitz=None,
          normals=False, resident=False):
@@ -353,21 +533,7 @@ def cast(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0
     t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
     low, first = lower(geometry)
     bound = _bound(low, first, lipschitz)
-    for name, x in (("origins", origins), ("directions", directions)):
-        if not isinstance(x, _engine.DeviceVectorField):
-            shape = np.shape(x)
-            if len(shape) != 2 or shape[0] != 3:
-                raise ValueError("%s must have shape (3, N); got %r" % (name, shape))
-    if not isinstance(directions, _engine.DeviceVectorField):
-        d32 = np.asarray(directions, dtype=np.float32).astype(np.float64)
-        off = np.abs((d32 * d32).sum(axis=0) - 1.0)
-        if off.size and not np.all(off <= 1e-5):
-            raise ValueError("directions must be unit vectors: ray %d has |d|^2 = %.9g" %
-                             (int(np.argmax(~(off <= 1e-5))), float((d32 * d32).sum(axis=0)[np.argmax(~(off <= 1e-5))])))
-    n_o = origins.n if isinstance(origins, _engine.DeviceVectorField) else int(np.shape(origins)[1])
-    n_d = directions.n if isinstance(directions, _engine.DeviceVectorField) else int(np.shape(directions)[1])
-    if n_o != n_d:
-        raise ValueError("%d origins for %d directions" % (n_o, n_d))
+    n_o = _check_rays(origins, directions)
     prog = _program(low)
     _engine.require_gpu()
     L = _engine.lib()
@@ -421,3 +587,73 @@ def render(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=25
     status = status.reshape(height, width)
     depth = np.where(status == HIT, t, np.float32(np.inf)).astype(np.float32)
     return Image(depth, status, steps.reshape(height, width), nrm, t=t, camera=camera, eps=float(eps), cone=float(cone))
+
+
+def spans(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0.0, max_steps=1024, lipschitz=None,
+          max_crossings=8, resident=False):
+    """Every crossing of arbitrary rays with the solid of `geometry`, and their chords. `origins`, `directions` as for
+    cast(). -> RaySpans. See the module text for the rule, the floor of `eps`, `lipschitz` and the refusals."""
+    t_min, t_max, eps, cone, max_steps, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
+    low, first = lower(geometry)
+    bound = _bound(low, first, lipschitz)
+    n = _check_rays(origins, directions)
+    prog = _program(low)
+    _engine.require_gpu()
+    L = _engine.lib()
+    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
+    vp = _engine._vp
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        co = stack.enter_context(device_coords(origins, "render"))
+        cd = stack.enter_context(device_coords(directions, "render"))
+        chord, cross, d_count, d_status, d_steps = _span_outputs(on_error, stack, n, k)
+        d_x, xstride = _cross_args(cross)
+        _engine.check(L.sdfk_span_rays_device(prog.handle, vp(co.ptr), co.stride, vp(cd.ptr), cd.stride, n, t_min, t_max, eps,
+                                              cone, float(np.float32(1.0 / bound)), max_steps, vp(chord.ptr), d_count.at(),
+                                              d_status.at(), d_steps.at(), d_x, xstride, k, None, config.mode),
+                      "sdfk_span_rays_device")
+        _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        status, steps = _small(n, d_status, d_steps)
+        count = d_count.download(np.empty(n, dtype=np.int32))
+        if resident:
+            on_error.pop_all()
+            return RaySpans(chord, count, status, steps, cross, t_min, t_max, k)
+        crossings = cross.download_rows() if k else np.empty((0, n), dtype=np.float32)
+        return RaySpans(chord.numpy(), count, status, steps, crossings, t_min, t_max, k)
+
+
+def thickness(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=1024, lipschitz=None, eps=None, cone=None,
+              max_crossings=0):
+    """Thickness / radiograph image of `geometry` from `camera`: the chord of every pixel's ray, generated in the kernel
+    from the camera record as in render(). `eps` / `cone` default to the pixel's footprint (Camera.footprint), `eps`
+    raised to its floor 2^-20 max(|t_min|, |t_max|) where the footprint's is smaller (the perspective camera's is 0).
+    -> ThicknessImage."""
+    width, height = camera._check(width, height)
+    fe, fc = camera.footprint(width, height)
+    if eps is None:
+        floor = SPAN_EPS_FLOOR * max(abs(float(t_min)), abs(float(t_max)))
+        eps = max(fe, float(np.nextafter(np.float32(floor), np.float32(np.inf)))) if np.isfinite(floor) else fe
+    cone = fc if cone is None else cone
+    t_min, t_max, eps, cone, max_steps, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
+    low, first = lower(geometry)
+    bound = _bound(low, first, lipschitz)
+    prog = _program(low)
+    _engine.require_gpu()
+    L = _engine.lib()
+    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
+    vp = _engine._vp
+    n = width * height
+    rec = camera.record(width, height)
+    with contextlib.ExitStack() as stack:
+        chord, cross, d_count, d_status, d_steps = _span_outputs(stack, stack, n, k)
+        d_x, xstride = _cross_args(cross)
+        _engine.check(L.sdfk_span_camera_device(prog.handle, _engine._ptr(rec), width, height, 1 if camera.ortho else 0, t_min,
+                                                t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(chord.ptr),
+                                                d_count.at(), d_status.at(), d_steps.at(), d_x, xstride, k, None, config.mode),
+                      "sdfk_span_camera_device")
+        _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        status, steps = _small(n, d_status, d_steps)
+        count = d_count.download(np.empty(n, dtype=np.int32))
+        chord = chord.numpy().reshape(height, width)
+        crossings = cross.download_rows().reshape(k, height, width) if k else None
+    return ThicknessImage(chord, count.reshape(height, width), status.reshape(height, width), steps.reshape(height, width),
+                          crossings, camera=camera, eps=float(eps), cone=float(cone), t_min=t_min, t_max=t_max)

@@ -106,6 +106,10 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
 #define SDFK_FLAVOUR_OCCUPANCY 11  /* sdfk_spec_occ_list / sdfk_spec_occ_all: the sample pass of sdfk_eval_grid_occupancy around
                                       the same body, one sub-sample per lane; as RAYS: no cull sites needed, no FLAGS / XY
                                       build, not part of sdfk_program_compile_check. */
+#define SDFK_FLAVOUR_SPANS 12      /* sdfk_spec_spans / sdfk_spec_spancam: every crossing of a ray with the solid and its chord
+                                      (sdfk_span_rays_device / sdfk_span_camera_device) around the same body; long chains get
+                                      the culled pair as RAYS does. As RAYS: no cull sites needed, no FLAGS / XY build, not
+                                      part of sdfk_program_compile_check. */
 /* OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (one bit per point, value <= threshold, instead of
    the field — what sdfk_eval_device_select / sdfk_eval_grid_select launch). A translation unit of its own: the field
    kernels carry none of it (as a run-time branch it cost the 20-primitive tree 10 % at 1025^3). */
@@ -560,6 +564,47 @@ int sdfk_trace_camera_device(sdfk_program* prog, const float* camera, int width,
                              float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_t,
                              unsigned char* d_status, int* d_steps, float* d_normals, int64_t normal_stride, void* stream,
                              int mode);
+
+/* ---- spans: every crossing of a ray with the solid, and its chord ---------------------------------------------------
+ * The march of sdfk_trace_rays_device does not stop at the surface: it records every change of sign of the field along
+ * the ray and adds up the length inside the solid { f <= 0 }. The field must be a distance bound as above. Per ray, in fp32:
+ *     t = t_min; count = 0; chord = 0
+ *     repeat at most max_steps times (evaluation e = 0, 1, ...):
+ *         f = field(o + t d);  inside = (f <= 0)
+ *         if e == 0: was = inside0 = inside; t_in = t_min                  (starting inside is not a crossing)
+ *         else if inside != was:
+ *             tc = t_prev + (t - t_prev) * |f_prev| / (|f_prev| + |f|)     (secant, one fmaf)
+ *             if count < max_crossings: crossings[count] = tc
+ *             count += 1;  if inside: t_in = tc  else: chord += tc - t_in;  was = inside
+ *         thr = max(eps, cone * t);  t_prev = t;  f_prev = f
+ *         t_next = t + max(|f| * inv_lipschitz, thr);  steps += 1
+ *         if not (t_next > t): status 2 (limit), stop                      (no progress in fp32)
+ *         t = t_next
+ *         if t > t_max: if was: chord += t_max - t_in;  status 0 (complete), stop
+ *     otherwise: status 2 (limit)
+ *     status 2, either way: if was: chord += t_prev - t_in                 (t_prev: the last evaluated parameter)
+ * A step of |f| / L cannot cross the surface, so every crossing lies inside a floor step of length thr: it is bracketed
+ * within thr, and only features thinner than thr along the ray can be missed, as a pair of crossings. eps must be large
+ * enough for t + eps > t in fp32 over [t_min, t_max] (2^-20 max(|t_min|, |t_max|) is), or rays end with status 2.
+ * Outputs, one entry per ray: d_chord (fp32), d_count (int32: all crossings, also those beyond max_crossings), d_status
+ * (1 byte: 0 or 2, plus 4 when the ray is inside the solid at t_min), d_steps (int32: evaluations made) and, unless
+ * d_crossings is NULL or max_crossings is 0, the first max_crossings crossing parameters as max_crossings rows of
+ * crossing_stride floats: crossing k of ray i at d_crossings[k * crossing_stride + i]. Rows from `count` on are NOT
+ * written: the caller initialises the array (NaN). Asynchronous on `stream`. `mode` selects the kernel exactly as for
+ * sdfk_trace_rays_device (SDFK_FLAVOUR_SPANS; interpreter and specialised kernels give the same bits; long chains are
+ * culled per wave except under SDFK_MODE_NOCULL, same bits). Programs with auxiliary fields are refused
+ * (sdfk_program_rays_check). Validated on the host, -1 and no launch: what sdfk_trace_rays_device refuses, a NULL
+ * d_chord / d_count / d_status / d_steps, max_crossings outside 0 ... 32, n < 0, crossing_stride < the ray count. */
+int sdfk_span_rays_device(sdfk_program* prog, const float* d_origins, int64_t origin_stride, const float* d_directions,
+                          int64_t direction_stride, int64_t n, float t_min, float t_max, float eps, float cone,
+                          float inv_lipschitz, int max_steps, float* d_chord, int* d_count, unsigned char* d_status,
+                          int* d_steps, float* d_crossings, int64_t crossing_stride, int max_crossings, void* stream, int mode);
+/* width x height rays generated in the kernel from `camera` as by sdfk_trace_camera_device; outputs in row-major pixel
+ * order, crossing k of pixel (ix, iy) at d_crossings[k * crossing_stride + iy * width + ix]; one tile of 8 x 8 pixels per wave. */
+int sdfk_span_camera_device(sdfk_program* prog, const float* camera, int width, int height, int orthographic, float t_min,
+                            float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_chord,
+                            int* d_count, unsigned char* d_status, int* d_steps, float* d_crossings, int64_t crossing_stride,
+                            int max_crossings, void* stream, int mode);
 
 /* ---- sub-voxel occupancy (aegolius_amd.occupancy; csrc/sdfk_occupancy.inc, csrc/sdfk_occdev.h) ---------------------
  * Per cell of the grid of the axis tables (flat index (i0 n1 + i1) n2 + i2), the fraction of its K = k0 k1 k2 sub-sample
