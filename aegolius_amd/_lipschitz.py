@@ -17,6 +17,14 @@ import numpy as np
 INF = float("inf")
 
 
+def given(lipschitz):
+    """A caller's `lipschitz=` argument as a float: an upper bound of |grad f| of the caller's own, finite and positive."""
+    L = float(lipschitz)
+    if not (np.isfinite(L) and L > 0.0):
+        raise ValueError("lipschitz must be finite and positive; got %r" % (lipschitz,))
+    return L
+
+
 def _norm2(m9):
     m = np.asarray(m9, dtype=np.float64).reshape(3, 3)
     if not np.all(np.isfinite(m)):

@@ -29,6 +29,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <variant>
 #include <vector>
 #include <dirent.h>
 #include <dlfcn.h>

@@ -664,7 +664,7 @@ static std::shared_ptr<SpecModule> get_module(sdfk_program* p, int device, int f
             }
         }
         if (he == hipSuccess && flavour == SDFK_FL_RAYS) {
-            // long chains come with a second pair of kernels that cull along the rays (sdfk_codegen.cpp: kRaysCull)
+            // long chains come with a second pair of kernels that cull along the rays (sdfk_raycull.h)
             if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_rays_cull") != hipSuccess ||
                 hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_raycam_cull") != hipSuccess) {
                 m->fn[2] = m->fn[3] = nullptr;

@@ -22,6 +22,7 @@
 // Every output element is written exactly once, by pass 2 or pass 3, with plain vector stores. After the last slab
 // sdfk_occ_total_kernel adds up fraction * K — integers — over the whole output: per-wave partial sums in a fixed order,
 // added on the host. Scratch: 8 B per slab cell (centre values, list), 8 B per 1024 slab cells (counts) and 32 KB.
+#include "sdfk_interpfield.h"
 #include "sdfk_occdev.h"
 
 template <int NC, int NV, typename SRC>

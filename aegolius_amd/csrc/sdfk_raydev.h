@@ -1,6 +1,8 @@
-// sdfk_raydev.h — sphere tracing of one program: the marching loop, the ray sources and the stencil normals. Shared
-// (like sdfk_access.h) by the interpreter ray kernel (sdfk_rays.inc) and, as embedded text, by the hiprtc-specialised
-// one (SDFK_FL_RAYS), so that the marching arithmetic is ONE piece of text: both kernels give the same bits.
+// sdfk_raydev.h — sphere tracing of one program: the marching loops, the ray sources and the stencil normals. Shared
+// (like sdfk_access.h) by the interpreter march kernel (sdfk_rays.inc) and, as embedded text, by the hiprtc-specialised
+// ones (SDFK_FL_RAYS, SDFK_FL_SPANS), so that the marching arithmetic is ONE piece of text: both kernels give the same bits.
+// One interface for every march: sdfk_march(src, field, opts, out), overloaded on the output record — SdfkHitOut: the first
+// hit (sdfk_trace, the rule below), SdfkSpanOut: every crossing and the chord (sdfk_trace_spans, the rule further down).
 //
 // The marching rule (aegolius_amd/render.py states it for users; tests/render_reference.py is its float64 copy):
 //     t = t_min
@@ -18,7 +20,7 @@
 // flow: `active` marks the lanes whose value will be used (the marching lanes; at the normal, the lanes that hit), and
 // the evaluations that follow stay within `reach` of this lane's p (0 along the ray; the stencil's reach at the normal).
 // A field may bound the active points of the wave and cull its members for them (the specialised chain-mode kernels:
-// sdfk_codegen.cpp, SdfkCullField); the interpreter's field ignores the call. The hook returns nothing and the value of
+// sdfk_raycull.h, SdfkCullField); the interpreter's field ignores the call. The hook returns nothing and the value of
 // an active lane must not depend on it: the marching arithmetic below is the same with and without.
 #ifndef SDFK_RAYDEV_H
 #define SDFK_RAYDEV_H
@@ -52,6 +54,24 @@ struct SdfkRaysArray {      // two (3, n) arrays, rows strided like d_co everywh
 };
 struct SdfkRaysCamera {     // rays generated from the record; every wave owns one tile of 8 x 8 pixels
     sdfk_camera cam;
+};
+
+// What a march writes per ray, and with it which march sdfk_march runs.
+struct SdfkHitOut {         // first hit: where the ray stopped, 0 miss / 1 hit / 2 step limit, advances made
+    float* __restrict__ t;
+    unsigned char* __restrict__ status;
+    int* __restrict__ steps;
+    float* __restrict__ n;  // the stencil normal, three rows nstride apart; null: none
+    long long nstride;
+};
+struct SdfkSpanOut {        // spans: length inside the solid, all crossings counted, status (| SDFK_SPAN_INSIDE0), evaluations
+    float* __restrict__ chord;
+    int* __restrict__ count;
+    unsigned char* __restrict__ status;
+    int* __restrict__ steps;
+    float* __restrict__ cross;  // the first max_crossings crossings, rows cstride apart (not read when max_crossings is 0)
+    long long cstride;
+    int max_crossings;
 };
 
 // -> is there a ray on this lane; its origin, direction and the index its results are stored at
@@ -259,5 +279,45 @@ static __device__ __forceinline__ void sdfk_trace_spans(const SRC& src, const FI
         out_steps[at] = steps;
     }
 }
+
+// The one interface of the marches: the output record selects the loop.
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkHitOut out) {
+    sdfk_trace(src, field, R, out.t, out.status, out.steps, out.n, out.nstride);
+}
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkSpanOut out) {
+    sdfk_trace_spans(src, field, R, out.max_crossings, out.chord, out.count, out.status, out.steps, out.cross, out.cstride);
+}
+
+// One specialised kernel of the generated text: NAME runs the march OUT (SDFK_HIT or SDFK_SPAN) on the rays of SRC
+// (SDFK_ARRAY: SdfkRaysArray; SDFK_CAMERA: the camera record, wrapped into SdfkRaysCamera) around FIELD (SDFK_FIELD_PLAIN,
+// or SDFK_FIELD_CULL of sdfk_raycull.h). Parameters: (PRM, TAB, the source, opts, the march's outputs, STATS) — STATS: the
+// counters of the statistics build of the culled first-hit kernels, null in every other launch. The outputs are flat
+// parameters handed straight to the loop: a by-value record spilled SGPRs (profiles/ray_family_refactor.txt).
+#define SDFK_ARRAY_PARAM SdfkRaysArray src
+#define SDFK_ARRAY_SOURCE
+#define SDFK_CAMERA_PARAM sdfk_camera cam
+#define SDFK_CAMERA_SOURCE const SdfkRaysCamera src = {cam};
+#define SDFK_HIT_PARAMS                                                                                           \
+    float *__restrict__ out_t, unsigned char *__restrict__ out_status, int *__restrict__ out_steps,               \
+        float *__restrict__ out_n, long long nstride
+#define SDFK_HIT_MARCH sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride)
+#define SDFK_SPAN_PARAMS                                                                                          \
+    int max_crossings, float *__restrict__ out_chord, int *__restrict__ out_count,                                \
+        unsigned char *__restrict__ out_status, int *__restrict__ out_steps, float *__restrict__ out_cross,       \
+        long long cstride
+#define SDFK_SPAN_MARCH \
+    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride)
+#define SDFK_FIELD_PLAIN const SdfkSpecField field = {PRM, TAB}
+#define SDFK_MARCH_KERNEL(NAME, SRC, OUT, FIELD)                                                                   \
+    extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void NAME(const float* __restrict__ PRM,              \
+                                                                      const float* __restrict__ TAB, SRC##_PARAM, \
+                                                                      sdfk_rayopts opts, OUT##_PARAMS,            \
+                                                                      unsigned long long* STATS) {                \
+        FIELD;                                                                                                     \
+        SRC##_SOURCE                                                                                               \
+        OUT##_MARCH;                                                                                               \
+    }
 
 #endif  // SDFK_RAYDEV_H

@@ -1,96 +1,30 @@
-// sdfk_rays.inc — sphere tracing of a program (included at the end of sdfk.hip; the loop itself: sdfk_raydev.h).
+// sdfk_rays.inc — sphere tracing of a program (included at the end of sdfk.hip; the loops themselves: sdfk_raydev.h).
 //
-//   * sdfk_rays_interp_kernel<NC, NV, SRC> : the interpreter's register machine as a __device__ evaluation of ONE point
-//     (SdfkInterpField: the opcode switch instantiated from sdfk_ops.def once more, as the dual and adjoint kernels do),
-//     called from the marching loop. One ray per lane; the code words are wave-uniform (scalar loads) because the
-//     loop's trip count is. SRC = SdfkRaysArray (two (3, n) arrays) or SdfkRaysCamera (rays generated from the camera
-//     record, one 8 x 8 pixel tile per wave). Register files as in sdfk_interp_kernel, and with the same outcome as its
-//     one-point-per-lane instantiations (compiler's resource remarks, all four instances: 57 VGPRs, 8 waves per SIMD):
-//     the small coordinate file stays in VGPRs and its three value registers, indexed by the wave-uniform operand
-//     fields, take 16 bytes of scratch per lane (sdfk_interp_kernel<1, 2, 3>: 16 as well); the full file takes 128.
-//   * the specialised flavour (SDFK_FL_RAYS, sdfk_codegen.cpp) wraps the generated sdfk_point<float> in the same loop;
-//     long hard unions (chain mode) get a second pair of kernels there that folds the chain over per-wave survivor
-//     lists in LDS (kRaysCull) — what SPECIALIZED / AUTO launch, NOCULL the plain pair; same bits.
-//   * sdfk_spans_interp_kernel / SDFK_FL_SPANS: the same field objects inside sdfk_trace_spans, the march that goes on
-//     through the surface (every crossing, the chord); selected, culled and served by the interpreter exactly as above.
-// Outputs per ray: t (fp32), status (1 byte: 0 miss, 1 hit, 2 step limit), steps (int32), optionally the stencil normal
-// (three strided rows). Plain vector stores, written once; no atomics, no LDS.
+//   * sdfk_march_interp_kernel<NC, NV, SRC, OUT> : the interpreter's register machine as a __device__ evaluation of ONE
+//     point (SdfkInterpField, sdfk_interpfield.h) called from the marching loop that OUT selects: SdfkHitOut the first hit,
+//     SdfkSpanOut the march that goes on through the surface (every crossing, the chord). One ray per lane; the code words
+//     are wave-uniform (scalar loads) because the loop's trip count is. SRC = SdfkRaysArray (two (3, n) arrays) or
+//     SdfkRaysCamera (rays generated from the camera record, one 8 x 8 pixel tile per wave). Register files as in
+//     sdfk_interp_kernel, and with the same outcome as its one-point-per-lane instantiations (compiler's resource remarks,
+//     all four first-hit instances: 57 VGPRs, 8 waves per SIMD): the small coordinate file stays in VGPRs and its three
+//     value registers, indexed by the wave-uniform operand fields, take 16 bytes of scratch per lane
+//     (sdfk_interp_kernel<1, 2, 3>: 16 as well); the full file takes 128.
+//   * the specialised flavours (SDFK_FL_RAYS, SDFK_FL_SPANS, sdfk_codegen.cpp) wrap the generated sdfk_point<float> in the
+//     same loops; long hard unions (chain mode) get a second pair of kernels there that folds the chain over per-wave
+//     survivor lists in LDS (sdfk_raycull.h) — what SPECIALIZED / AUTO launch, NOCULL the plain pair; same bits.
+//   * the host side is one path for both marches: an entry point fills a MarchRequest, march_run picks and launches.
+// Outputs per ray, first hit: t (fp32), status (1 byte: 0 miss, 1 hit, 2 step limit), steps (int32), optionally the
+// stencil normal (three strided rows). Plain vector stores, written once; no atomics, no LDS.
+#include "sdfk_interpfield.h"
 #include "sdfk_raydev.h"
 
-template <int NC, int NV>
-struct SdfkInterpField {
-    const uint2* __restrict__ code;
-    int n_instr;
-    const float* __restrict__ prm;
-    const float* __restrict__ tab;
-    int result_reg;
-    __device__ __forceinline__ void prepare(V3, float, bool, float) const {}   // (the wave-level hook: nothing to cull here)
-    __device__ __forceinline__ float operator()(V3 p0) const {
-        constexpr bool SPLIT = NC <= SDFK_NC_SMALL;             // (see sdfk_interp_kernel)
-        float CX[SPLIT ? NC : 1], CY[SPLIT ? NC : 1], CZ[SPLIT ? NC : 1];
-        V3 CS[SPLIT ? 1 : NC];
-        float V[NV];
-#define SDFK_RCGET(r) (SPLIT ? V3{CX[SPLIT ? (r) : 0], CY[SPLIT ? (r) : 0], CZ[SPLIT ? (r) : 0]} : CS[SPLIT ? 0 : (r)])
-#define SDFK_RCSET(r, q)                                                                             \
-    do {                                                                                             \
-        const V3 q_ = (q);                                                                           \
-        if constexpr (SPLIT) { CX[SPLIT ? (r) : 0] = q_.x; CY[SPLIT ? (r) : 0] = q_.y; CZ[SPLIT ? (r) : 0] = q_.z; } \
-        else CS[SPLIT ? 0 : (r)] = q_;                                                               \
-    } while (0)
-        SDFK_RCSET(0, p0);
-        for (int pc = 0; pc < n_instr; ++pc) {
-            const uint2 ins = code[pc];                         // wave-uniform: scalar loads
-            const unsigned op = ins.x & 255u, a = (ins.x >> 8) & 255u, b = (ins.x >> 16) & 255u, c = ins.x >> 24;
-            const float* __restrict__ P = prm + ins.y;
-            switch (op) {
-#define SDFK_REXEC_C_C(F) SDFK_RCSET(a, F(SDFK_RCGET(b), P, tab, (int)c))
-#define SDFK_REXEC_V_C(F) V[a] = F(SDFK_RCGET(b), P, tab)
-#define SDFK_REXEC_V_V(F) V[a] = F(V[b], P)
-#define SDFK_REXEC_V_VV(F) V[a] = F(V[b], V[c], P)
-#define SDFK_OP(NAME, KIND, NP, FUNC) \
-    case SDFK_OP_##NAME:              \
-        SDFK_REXEC_##KIND(FUNC);      \
-        break;
-#include "sdfk_ops.def"
-#undef SDFK_OP
-                default:                                        // (V_FIELD: refused on the host, sdfk_program_rays_check)
-                    break;
-            }
-        }
-        return V[result_reg];
-#undef SDFK_REXEC_C_C
-#undef SDFK_REXEC_V_C
-#undef SDFK_REXEC_V_V
-#undef SDFK_REXEC_V_VV
-#undef SDFK_RCGET
-#undef SDFK_RCSET
-    }
-};
-
-template <int NC, int NV, typename SRC>
-__global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_rays_interp_kernel(const uint2* __restrict__ code, int n_instr,
-                                                                         const float* __restrict__ prm,
-                                                                         const float* __restrict__ tab, int result_reg,
-                                                                         SRC src, sdfk_rayopts opts, float* __restrict__ out_t,
-                                                                         unsigned char* __restrict__ out_status,
-                                                                         int* __restrict__ out_steps,
-                                                                         float* __restrict__ out_n, long long nstride) {
-    const SdfkInterpField<NC, NV> field = {code, n_instr, prm, tab, result_reg};
-    sdfk_trace(src, field, opts, out_t, out_status, out_steps, out_n, nstride);
-}
-
-// The span march (sdfk_trace_spans) around the same field object: every crossing and the chord instead of the first hit.
-template <int NC, int NV, typename SRC>
-__global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_spans_interp_kernel(const uint2* __restrict__ code, int n_instr,
+template <int NC, int NV, typename SRC, typename OUT>
+__global__ __launch_bounds__(SDFK_RAY_BLOCK) void sdfk_march_interp_kernel(const uint2* __restrict__ code, int n_instr,
                                                                           const float* __restrict__ prm,
                                                                           const float* __restrict__ tab, int result_reg,
-                                                                          SRC src, sdfk_rayopts opts, int max_crossings,
-                                                                          float* __restrict__ out_chord, int* __restrict__ out_count,
-                                                                          unsigned char* __restrict__ out_status,
-                                                                          int* __restrict__ out_steps,
-                                                                          float* __restrict__ out_cross, long long cstride) {
+                                                                          SRC src, sdfk_rayopts opts, OUT out) {
     const SdfkInterpField<NC, NV> field = {code, n_instr, prm, tab, result_reg};
-    sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride);
+    sdfk_march(src, field, opts, out);
 }
 
 // ---- host side ----------------------------------------------------------------------------------
@@ -164,50 +98,112 @@ static int rays_stats_collect(unsigned long long* b, hipStream_t stream) {
     return 0;
 }
 
-// array rays (cam == nullptr) or camera rays; `count` = rays (array) or pixels (camera)
-static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, const sdfk_camera* cam, long long count,
-                    const sdfk_rayopts& opts, float* d_t, unsigned char* d_status, int* d_steps, float* d_normals,
-                    long long nstride, void* stream_, int mode) {
+// ---- one request, one runner ---------------------------------------------------------------------------------------------
+struct MarchRequest {
+    const char* who;                                  // the entry point, for messages
+    sdfk_program* p;
+    std::variant<SdfkRaysArray, sdfk_camera> src;     // array rays (count = rays), or a parsed camera (count = pixels)
+    long long count;
+    sdfk_rayopts opts;
+    std::variant<SdfkHitOut, SdfkSpanOut> out;        // the output record, which also says which march
+    void* stream;
+    int mode;
+};
+
+// the caller's 12 floats {eye, fwd, du, dv} and the image size -> the kernels' record
+static int camera_record(const char* who, const float* camera, int width, int height, int orthographic, sdfk_camera* c) {
+    const std::string w = who;
+    if (!camera) return fail(-1, w + ": null camera");
+    if (width < 0 || height < 0 || width > 32768 || height > 32768) return fail(-1, w + ": image sizes from 0 to 32768");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(camera[i])) return fail(-1, w + ": the camera record is not finite");
+    for (int i = 0; i < 3; ++i)
+        c->eye[i] = camera[i], c->fwd[i] = camera[3 + i], c->du[i] = camera[6 + i], c->dv[i] = camera[9 + i];
+    c->inv_w = width ? 1.0f / (float)width : 0.0f;
+    c->inv_h = height ? 1.0f / (float)height : 0.0f;
+    c->width = width, c->height = height, c->ortho = orthographic ? 1 : 0;
+    return 0;
+}
+static int ray_arrays(const char* who, const float* d_origins, int64_t origin_stride, const float* d_directions,
+                      int64_t direction_stride, int64_t n, SdfkRaysArray* a) {
+    const std::string w = who;
+    if (n < 0) return fail(-1, w + ": negative ray count");
+    if (n > 0 && (!d_origins || !d_directions)) return fail(-1, w + ": null ray pointer");
+    if (origin_stride < n || direction_stride < n) return fail(-1, w + ": row stride smaller than the ray count");
+    *a = {d_origins, (long long)origin_stride, d_directions, (long long)direction_stride, (long long)n};
+    return 0;
+}
+static int hit_outputs(const char* who, float* d_t, unsigned char* d_status, int* d_steps, float* d_normals,
+                       int64_t normal_stride, long long count, SdfkHitOut* out) {
     const std::string w = who;
     if (!d_t || !d_status || !d_steps) return fail(-1, w + ": null output pointer");
-    if (d_normals && nstride < count) return fail(-1, w + ": normal row stride smaller than the ray count");
+    if (d_normals && normal_stride < count) return fail(-1, w + ": normal row stride smaller than the ray count");
+    *out = {d_t, d_status, d_steps, d_normals, (long long)normal_stride};
+    return 0;
+}
+static int span_outputs(const char* who, float* d_chord, int* d_count, unsigned char* d_status, int* d_steps,
+                        float* d_crossings, int64_t crossing_stride, int max_crossings, long long count, SdfkSpanOut* out) {
+    const std::string w = who;
+    if (!d_chord || !d_count || !d_status || !d_steps) return fail(-1, w + ": null output pointer");
+    if (max_crossings < 0 || max_crossings > SDFK_SPAN_MAX_CROSSINGS)
+        return fail(-1, w + ": max_crossings from 0 to " + std::to_string(SDFK_SPAN_MAX_CROSSINGS));
+    if (d_crossings && max_crossings > 0 && crossing_stride < count)
+        return fail(-1, w + ": crossing row stride smaller than the ray count");
+    // (no array: the crossings are counted and not stored)
+    *out = {d_chord, d_count, d_status, d_steps, d_crossings, (long long)crossing_stride, d_crossings ? max_crossings : 0};
+    return 0;
+}
+
+// The program's check, the kernel that serves the call (pick_kernel) and its launch. The two marches differ in the flavour,
+// in pick_kernel's text and in the counters of the statistics build, which only the culled first-hit kernels feed.
+static int march_run(const MarchRequest& r) {
     int bad = -1;
-    const int chk = sdfk_program_rays_check(p, &bad);
-    if (chk) return fail(chk < 0 ? chk : -3, w + ": " + g_err);
-    if (count == 0) return 0;
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
+    const int chk = sdfk_program_rays_check(r.p, &bad);
+    if (chk) return fail(chk < 0 ? chk : -3, std::string(r.who) + ": " + g_err);
+    if (r.count == 0) return 0;
+    const int mode = r.mode == SDFK_MODE_AUTO ? g_default_mode : r.mode;
     LaunchCtx x;
-    int rc = launch_ctx(p, stream_, &x);
+    int rc = launch_ctx(r.p, r.stream, &x);
     if (rc) return rc;
     hipStream_t stream = x.stream;
+    const sdfk_camera* cam = std::get_if<sdfk_camera>(&r.src);
+    const bool spans = std::holds_alternative<SdfkSpanOut>(r.out);
     unsigned blocks;
     if (cam) {
         const long long tiles = (long long)((cam->width + 7) / 8) * ((cam->height + 7) / 8);
         blocks = (unsigned)((tiles + SDFK_RAY_BLOCK / 64 - 1) / (SDFK_RAY_BLOCK / 64));
     } else {
-        blocks = (unsigned)((count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
+        blocks = (unsigned)((r.count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
     }
     std::shared_ptr<SpecModule> sk;                            // (a failed build falls back in AUTO only)
-    rc = pick_kernel(p, x.device, SDFK_FL_RAYS, 0, mode, mode == SDFK_MODE_AUTO, "ray kernel", false, &sk);
+    rc = pick_kernel(r.p, x.device, spans ? SDFK_FL_SPANS : SDFK_FL_RAYS, 0, mode, mode == SDFK_MODE_AUTO,
+                     spans ? "span kernel" : "ray kernel", false, &sk);
     if (rc) return rc;
     const float* prm = x.prm;
     const float* tab = x.tab;
-    sdfk_rayopts o = opts;
     if (sk) {
-        // the culled pair (long chains only) unless the caller asked for the kernel without culling; one more argument,
-        // the counters of the statistics build (null otherwise)
+        // the culled pair (long chains only) unless the caller asked for the kernel without culling
         const bool cull = mode != SDFK_MODE_NOCULL && sk->fn[2] && sk->fn[3];
         unsigned long long* stats = nullptr;
-        if (cull && g_rays_stats_on.load()) {
+        if (cull && !spans && g_rays_stats_on.load()) {
             rc = rays_stats_buffer(&stats, stream);
             if (rc) return rc;
         }
-        sdfk_camera c;
-        SdfkRaysArray a;
-        void* src = cam ? (void*)&c : (void*)&a;
-        if (cam) c = *cam;
-        else a = *arr;
-        void* args[] = {&prm, &tab, src, &o, &d_t, &d_status, &d_steps, &d_normals, &nstride, &stats};
+        // (PRM, TAB, source, opts, the march's outputs in the order of SDFK_HIT_PARAMS / SDFK_SPAN_PARAMS, STATS)
+        auto src = r.src;
+        auto out = r.out;
+        sdfk_rayopts opts = r.opts;
+        void* args[12] = {&prm, &tab, std::visit([](auto& s) { return (void*)&s; }, src), &opts};
+        int n = 4;
+        if (SdfkSpanOut* s = std::get_if<SdfkSpanOut>(&out)) {
+            for (void* a : {(void*)&s->max_crossings, (void*)&s->chord, (void*)&s->count, (void*)&s->status, (void*)&s->steps,
+                            (void*)&s->cross, (void*)&s->cstride})
+                args[n++] = a;
+        } else {
+            SdfkHitOut* h = std::get_if<SdfkHitOut>(&out);
+            for (void* a : {(void*)&h->t, (void*)&h->status, (void*)&h->steps, (void*)&h->n, (void*)&h->nstride}) args[n++] = a;
+        }
+        args[n++] = &stats;
         HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (cam ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
                                      nullptr));
         if (stats) {
@@ -216,35 +212,34 @@ static int rays_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, 
         }
         return 0;
     }
-    auto launch = [&](auto src) {
+    auto launch = [&](auto src, auto out) {
         using SRC = decltype(src);
-#define SDFK_RAYS_GO(NC, NV) hipLaunchKernelGGL((sdfk_rays_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream, \
-                                                x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, o, d_t, d_status, d_steps, d_normals, nstride)
-        SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_RAYS_GO);
-#undef SDFK_RAYS_GO
+        using OUT = decltype(out);
+#define SDFK_MARCH_GO(NC, NV) hipLaunchKernelGGL((sdfk_march_interp_kernel<NC, NV, SRC, OUT>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream, \
+                                                 x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, r.opts, out)
+        SDFK_REGFILE(r.p, SDFK_NC, SDFK_NV, SDFK_MARCH_GO);
+#undef SDFK_MARCH_GO
     };
-    if (cam) launch(SdfkRaysCamera{*cam});
-    else launch(*arr);
+    std::visit([&](auto out) {
+        if (cam) launch(SdfkRaysCamera{*cam}, out);
+        else launch(std::get<SdfkRaysArray>(r.src), out);
+    }, r.out);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
+// ---- the entry points: each fills a request, in the order its checks report ------------------------------------------------
 extern "C" int sdfk_trace_rays_device(sdfk_program* p, const float* d_origins, int64_t origin_stride,
                                       const float* d_directions, int64_t direction_stride, int64_t n, float t_min,
                                       float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_t,
                                       unsigned char* d_status, int* d_steps, float* d_normals, int64_t normal_stride,
                                       void* stream, int mode) {
     if (!p) return fail(-1, "null program");
-    if (n < 0) return fail(-1, "sdfk_trace_rays_device: negative ray count");
-    if (n > 0 && (!d_origins || !d_directions)) return fail(-1, "sdfk_trace_rays_device: null ray pointer");
-    if (origin_stride < n || direction_stride < n)
-        return fail(-1, "sdfk_trace_rays_device: row stride smaller than the ray count");
-    sdfk_rayopts o;
-    int rc = rays_options("sdfk_trace_rays_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
-    if (rc) return rc;
-    SdfkRaysArray a = {d_origins, (long long)origin_stride, d_directions, (long long)direction_stride, (long long)n};
-    return rays_run("sdfk_trace_rays_device", p, &a, nullptr, n, o, d_t, d_status, d_steps, d_normals,
-                    (long long)normal_stride, stream, mode);
+    MarchRequest r = {"sdfk_trace_rays_device", p, SdfkRaysArray{}, (long long)n, {}, SdfkHitOut{}, stream, mode};
+    int rc = ray_arrays(r.who, d_origins, origin_stride, d_directions, direction_stride, n, &std::get<SdfkRaysArray>(r.src));
+    if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
+    if (!rc) rc = hit_outputs(r.who, d_t, d_status, d_steps, d_normals, normal_stride, r.count, &std::get<SdfkHitOut>(r.out));
+    return rc ? rc : march_run(r);
 }
 
 extern "C" int sdfk_trace_camera_device(sdfk_program* p, const float* camera, int width, int height, int orthographic,
@@ -252,79 +247,11 @@ extern "C" int sdfk_trace_camera_device(sdfk_program* p, const float* camera, in
                                         float* d_t, unsigned char* d_status, int* d_steps, float* d_normals,
                                         int64_t normal_stride, void* stream, int mode) {
     if (!p) return fail(-1, "null program");
-    if (!camera) return fail(-1, "sdfk_trace_camera_device: null camera");
-    if (width < 0 || height < 0 || width > 32768 || height > 32768)
-        return fail(-1, "sdfk_trace_camera_device: image sizes from 0 to 32768");
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(camera[i])) return fail(-1, "sdfk_trace_camera_device: the camera record is not finite");
-    sdfk_rayopts o;
-    int rc = rays_options("sdfk_trace_camera_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
-    if (rc) return rc;
-    sdfk_camera c;
-    for (int i = 0; i < 3; ++i) c.eye[i] = camera[i], c.fwd[i] = camera[3 + i], c.du[i] = camera[6 + i], c.dv[i] = camera[9 + i];
-    c.inv_w = width ? 1.0f / (float)width : 0.0f;
-    c.inv_h = height ? 1.0f / (float)height : 0.0f;
-    c.width = width, c.height = height, c.ortho = orthographic ? 1 : 0;
-    return rays_run("sdfk_trace_camera_device", p, nullptr, &c, (long long)width * height, o, d_t, d_status, d_steps,
-                    d_normals, (long long)normal_stride, stream, mode);
-}
-
-// ---- spans: every crossing and the chord (sdfk_trace_spans) --------------------------------------------------------------
-// array rays (cam == nullptr) or camera rays, as rays_run; the kernel follows pick_kernel exactly as there
-static int spans_run(const char* who, sdfk_program* p, const SdfkRaysArray* arr, const sdfk_camera* cam, long long count,
-                     const sdfk_rayopts& opts, float* d_chord, int* d_count, unsigned char* d_status, int* d_steps,
-                     float* d_cross, long long cstride, int max_crossings, void* stream_, int mode) {
-    const std::string w = who;
-    if (!d_chord || !d_count || !d_status || !d_steps) return fail(-1, w + ": null output pointer");
-    if (max_crossings < 0 || max_crossings > SDFK_SPAN_MAX_CROSSINGS)
-        return fail(-1, w + ": max_crossings from 0 to " + std::to_string(SDFK_SPAN_MAX_CROSSINGS));
-    if (d_cross && max_crossings > 0 && cstride < count) return fail(-1, w + ": crossing row stride smaller than the ray count");
-    int K = d_cross ? max_crossings : 0;                       // (no array: the crossings are counted and not stored)
-    int bad = -1;
-    const int chk = sdfk_program_rays_check(p, &bad);
-    if (chk) return fail(chk < 0 ? chk : -3, w + ": " + g_err);
-    if (count == 0) return 0;
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    LaunchCtx x;
-    int rc = launch_ctx(p, stream_, &x);
-    if (rc) return rc;
-    hipStream_t stream = x.stream;
-    unsigned blocks;
-    if (cam) {
-        const long long tiles = (long long)((cam->width + 7) / 8) * ((cam->height + 7) / 8);
-        blocks = (unsigned)((tiles + SDFK_RAY_BLOCK / 64 - 1) / (SDFK_RAY_BLOCK / 64));
-    } else {
-        blocks = (unsigned)((count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
-    }
-    std::shared_ptr<SpecModule> sk;                            // (a failed build falls back in AUTO only)
-    rc = pick_kernel(p, x.device, SDFK_FL_SPANS, 0, mode, mode == SDFK_MODE_AUTO, "span kernel", false, &sk);
-    if (rc) return rc;
-    const float* prm = x.prm;
-    const float* tab = x.tab;
-    sdfk_rayopts o = opts;
-    if (sk) {
-        const bool cull = mode != SDFK_MODE_NOCULL && sk->fn[2] && sk->fn[3];   // the culled pair: long chains only
-        sdfk_camera c;
-        SdfkRaysArray a;
-        void* src = cam ? (void*)&c : (void*)&a;
-        if (cam) c = *cam;
-        else a = *arr;
-        void* args[] = {&prm, &tab, src, &o, &K, &d_chord, &d_count, &d_status, &d_steps, &d_cross, &cstride};
-        HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (cam ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
-                                     nullptr));
-        return 0;
-    }
-    auto launch = [&](auto src) {
-        using SRC = decltype(src);
-#define SDFK_SPANS_GO(NC, NV) hipLaunchKernelGGL((sdfk_spans_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_RAY_BLOCK), 0, stream, \
-                                                 x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, o, K, d_chord, d_count, d_status, d_steps, d_cross, cstride)
-        SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_SPANS_GO);
-#undef SDFK_SPANS_GO
-    };
-    if (cam) launch(SdfkRaysCamera{*cam});
-    else launch(*arr);
-    HIPCHK(hipGetLastError());
-    return 0;
+    MarchRequest r = {"sdfk_trace_camera_device", p, sdfk_camera{}, (long long)width * height, {}, SdfkHitOut{}, stream, mode};
+    int rc = camera_record(r.who, camera, width, height, orthographic, &std::get<sdfk_camera>(r.src));
+    if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
+    if (!rc) rc = hit_outputs(r.who, d_t, d_status, d_steps, d_normals, normal_stride, r.count, &std::get<SdfkHitOut>(r.out));
+    return rc ? rc : march_run(r);
 }
 
 extern "C" int sdfk_span_rays_device(sdfk_program* p, const float* d_origins, int64_t origin_stride, const float* d_directions,
@@ -333,16 +260,11 @@ extern "C" int sdfk_span_rays_device(sdfk_program* p, const float* d_origins, in
                                      int* d_steps, float* d_crossings, int64_t crossing_stride, int max_crossings, void* stream,
                                      int mode) {
     if (!p) return fail(-1, "null program");
-    if (n < 0) return fail(-1, "sdfk_span_rays_device: negative ray count");
-    if (n > 0 && (!d_origins || !d_directions)) return fail(-1, "sdfk_span_rays_device: null ray pointer");
-    if (origin_stride < n || direction_stride < n)
-        return fail(-1, "sdfk_span_rays_device: row stride smaller than the ray count");
-    sdfk_rayopts o;
-    int rc = rays_options("sdfk_span_rays_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
-    if (rc) return rc;
-    SdfkRaysArray a = {d_origins, (long long)origin_stride, d_directions, (long long)direction_stride, (long long)n};
-    return spans_run("sdfk_span_rays_device", p, &a, nullptr, n, o, d_chord, d_count, d_status, d_steps, d_crossings,
-                     (long long)crossing_stride, max_crossings, stream, mode);
+    MarchRequest r = {"sdfk_span_rays_device", p, SdfkRaysArray{}, (long long)n, {}, SdfkSpanOut{}, stream, mode};
+    int rc = ray_arrays(r.who, d_origins, origin_stride, d_directions, direction_stride, n, &std::get<SdfkRaysArray>(r.src));
+    if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
+    if (!rc) rc = span_outputs(r.who, d_chord, d_count, d_status, d_steps, d_crossings, crossing_stride, max_crossings, r.count, &std::get<SdfkSpanOut>(r.out));
+    return rc ? rc : march_run(r);
 }
 
 extern "C" int sdfk_span_camera_device(sdfk_program* p, const float* camera, int width, int height, int orthographic,
@@ -350,19 +272,9 @@ extern "C" int sdfk_span_camera_device(sdfk_program* p, const float* camera, int
                                        float* d_chord, int* d_count, unsigned char* d_status, int* d_steps, float* d_crossings,
                                        int64_t crossing_stride, int max_crossings, void* stream, int mode) {
     if (!p) return fail(-1, "null program");
-    if (!camera) return fail(-1, "sdfk_span_camera_device: null camera");
-    if (width < 0 || height < 0 || width > 32768 || height > 32768)
-        return fail(-1, "sdfk_span_camera_device: image sizes from 0 to 32768");
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(camera[i])) return fail(-1, "sdfk_span_camera_device: the camera record is not finite");
-    sdfk_rayopts o;
-    int rc = rays_options("sdfk_span_camera_device", t_min, t_max, eps, cone, inv_lipschitz, max_steps, &o);
-    if (rc) return rc;
-    sdfk_camera c;
-    for (int i = 0; i < 3; ++i) c.eye[i] = camera[i], c.fwd[i] = camera[3 + i], c.du[i] = camera[6 + i], c.dv[i] = camera[9 + i];
-    c.inv_w = width ? 1.0f / (float)width : 0.0f;
-    c.inv_h = height ? 1.0f / (float)height : 0.0f;
-    c.width = width, c.height = height, c.ortho = orthographic ? 1 : 0;
-    return spans_run("sdfk_span_camera_device", p, nullptr, &c, (long long)width * height, o, d_chord, d_count, d_status,
-                     d_steps, d_crossings, (long long)crossing_stride, max_crossings, stream, mode);
+    MarchRequest r = {"sdfk_span_camera_device", p, sdfk_camera{}, (long long)width * height, {}, SdfkSpanOut{}, stream, mode};
+    int rc = camera_record(r.who, camera, width, height, orthographic, &std::get<sdfk_camera>(r.src));
+    if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
+    if (!rc) rc = span_outputs(r.who, d_chord, d_count, d_status, d_steps, d_crossings, crossing_stride, max_crossings, r.count, &std::get<SdfkSpanOut>(r.out));
+    return rc ? rc : march_run(r);
 }

@@ -57,6 +57,7 @@ import numpy as np
 
 from . import _engine
 from ._eval import config
+from ._lipschitz import given
 from .mesh import _level, _tables
 from .render import _program, lower
 
@@ -161,10 +162,7 @@ def _lipschitz(low, lipschitz):
         if np.isnan(L) or L < 0.0:
             raise ValueError("the lowering's Lipschitz bound is %r" % (L,))
         return L                                                # (inf: nothing is skipped; 0: a constant field)
-    L = float(lipschitz)
-    if not (np.isfinite(L) and L > 0.0):
-        raise ValueError("lipschitz must be finite and positive; got %r" % (lipschitz,))
-    return L
+    return given(lipschitz)
 
 
 def fractions(geometry, axes, samples=4, level=0.0, lipschitz=None, resident=False, timings=None, _slab_cells=0):

@@ -137,10 +137,7 @@ def lower(geometry):
 
 def _bound(low, first, lipschitz):
     if lipschitz is not None:
-        L = float(lipschitz)
-        if not (np.isfinite(L) and L > 0.0):
-            raise ValueError("lipschitz must be finite and positive; got %r" % (lipschitz,))
-        return L
+        return _lipschitz.given(lipschitz)
     if not np.isfinite(low.lipschitz):
         if first is not None:
             where = "instruction %d (%s, from %s) has no finite Lipschitz bound" % first
@@ -470,10 +467,9 @@ def _small(n, d_status, d_steps):
     return d_status.download(np.empty(n, dtype=np.uint8)), d_steps.download(np.empty(n, dtype=np.int32))
 
 
-def _normal_args(nrm):
-    if nrm is None:
-        return None, 0
-    return _engine._vp(nrm.ptr), nrm.stride
+def _rows(rows):
+    """The (pointer, row stride) arguments of an optional strided output: the normals, the crossings."""
+    return (None, 0) if rows is None else (rows.at(), rows.stride)
 
 
 def _span_outputs(fields, scratch, n, k):
@@ -497,12 +493,6 @@ def _span_outputs(fields, scratch, n, k):
     return chord, cross, d_count, d_status, d_steps
 
 
-def _cross_args(cross):
-    if cross is None:
-        return None, 0
-    return cross.at(), cross.stride
-
-
 def _check_rays(origins, directions):
     """The checks of cast() on a pair of ray arrays -> the number of rays."""
     for name, x in (("origins", origins), ("directions", directions)):
@@ -524,31 +514,66 @@ def _check_rays(origins, directions):
     return n_o
 
 
+def _lowered(geometry, lipschitz):
+    """-> (the geometry's lowered program, float32(1 / L) of its Lipschitz bound or of the caller's `lipschitz`)."""
+    low, first = lower(geometry)
+    return low, float(np.float32(1.0 / _bound(low, first, lipschitz)))
+
+
+def _on_device(low):
+    """-> the program of `low`, checked for the marches, with the device selected."""
+    prog = _program(low)
+    _engine.require_gpu()
+    _engine.check(_engine.lib().sdfk_set_device(config.device), "sdfk_set_device")
+    return prog
+
+
+def _setup(geometry, lipschitz):
+    """What every march needs of its geometry -> (the program, float32(1 / L)), with the device selected."""
+    low, inv = _lowered(geometry, lipschitz)
+    return _on_device(low), inv
+
+
+@contextlib.contextmanager
+def _source(rays=None, camera=None, size=None):
+    """The rays of a march -> the arguments of its entry point between the program and the options: `rays` = (origins,
+    directions, their number) for the *_rays_device entry points, host arrays being on the device for the duration, or a
+    camera and its image `size` = (width, height) for the *_camera_device ones."""
+    if camera is None:
+        with device_coords(rays[0], "render") as co, device_coords(rays[1], "render") as cd:
+            yield _engine._vp(co.ptr), co.stride, _engine._vp(cd.ptr), cd.stride, rays[2]
+    else:
+        rec = camera.record(*size)                              # (lives as long as the block that uses its address)
+        yield _engine._ptr(rec), size[0], size[1], 1 if camera.ortho else 0
+
+
+def _march(entry, prog, source, options, inv_lipschitz, outputs, n, d_status, d_steps):
+    """One call of the entry point `entry` (sdfk_{trace,span}_{rays,camera}_device): the program, the source's arguments,
+    the options every march shares, the march's own `outputs`, the default stream and the configured mode; waits for it.
+    -> (status, steps) on the host."""
+    t_min, t_max, eps, cone, max_steps = options
+    L = _engine.lib()
+    _engine.check(getattr(L, entry)(prog.handle, *source, t_min, t_max, eps, cone, inv_lipschitz, max_steps, *outputs, None,
+                                    config.mode), entry)
+    _engine.check(L.sdfk_sync(None), "sdfk_sync")
+    return _small(n, d_status, d_steps)
+
+
 # ---- public interface ---------------------------------------------------------------------------------------------------
 def cast(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0.0, max_steps=256, lipschitz=None,
          normals=False, resident=False):
     """First hit of arbitrary rays with `geometry`. `origins`, `directions`: (3, N) host arrays (used as float32) or
     DeviceVectorFields; the directions must be unit vectors (checked for host arrays: | |d|^2 - 1 | <= 1e-5).
     -> RayHits. See the module text for the marching rule, `lipschitz` and the refusals."""
-    t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
-    low, first = lower(geometry)
-    bound = _bound(low, first, lipschitz)
-    n_o = _check_rays(origins, directions)
-    prog = _program(low)
-    _engine.require_gpu()
-    L = _engine.lib()
-    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
-    vp = _engine._vp
+    options = _options(t_min, t_max, eps, cone, max_steps)
+    low, inv = _lowered(geometry, lipschitz)
+    n = _check_rays(origins, directions)                        # (before anything asks for the GPU)
+    prog = _on_device(low)
     with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
-        co = stack.enter_context(device_coords(origins, "render"))
-        cd = stack.enter_context(device_coords(directions, "render"))
-        t, nrm, d_status, d_steps = _outputs(on_error, stack, n_o, normals)
-        d_n, nstride = _normal_args(nrm)
-        _engine.check(L.sdfk_trace_rays_device(prog.handle, vp(co.ptr), co.stride, vp(cd.ptr), cd.stride, n_o, t_min, t_max,
-                                               eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(t.ptr), d_status.at(),
-                                               d_steps.at(), d_n, nstride, None, config.mode), "sdfk_trace_rays_device")
-        _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = _small(n_o, d_status, d_steps)
+        source = stack.enter_context(_source(rays=(origins, directions, n)))
+        t, nrm, d_status, d_steps = _outputs(on_error, stack, n, normals)
+        status, steps = _march("sdfk_trace_rays_device", prog, source, options, inv,
+                               (t.at(), d_status.at(), d_steps.at()) + _rows(nrm), n, d_status, d_steps)
         if resident:
             on_error.pop_all()
             return RayHits(t, status, steps, nrm, origins, directions)
@@ -563,25 +588,15 @@ def render(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps=25
     fe, fc = camera.footprint(width, height)
     eps = fe if eps is None else eps
     cone = fc if cone is None else cone
-    t_min, t_max, eps, cone, max_steps = _options(t_min, t_max, eps, cone, max_steps)
-    low, first = lower(geometry)
-    bound = _bound(low, first, lipschitz)
-    prog = _program(low)
-    _engine.require_gpu()
-    L = _engine.lib()
-    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
-    vp = _engine._vp
-    n = width * height
-    rec = camera.record(width, height)
+    options = _options(t_min, t_max, eps, cone, max_steps)
+    eps, cone = options[2:4]                                    # (as the kernel sees them)
+    prog, inv = _setup(geometry, lipschitz)
     with contextlib.ExitStack() as stack:
+        source = stack.enter_context(_source(camera=camera, size=(width, height)))
+        n = width * height
         t, nrm, d_status, d_steps = _outputs(stack, stack, n, normals)
-        d_n, nstride = _normal_args(nrm)
-        _engine.check(L.sdfk_trace_camera_device(prog.handle, _engine._ptr(rec), width, height, 1 if camera.ortho else 0, t_min,
-                                                 t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(t.ptr),
-                                                 d_status.at(), d_steps.at(), d_n, nstride, None, config.mode),
-                      "sdfk_trace_camera_device")
-        _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = _small(n, d_status, d_steps)
+        status, steps = _march("sdfk_trace_camera_device", prog, source, options, inv,
+                               (t.at(), d_status.at(), d_steps.at()) + _rows(nrm), n, d_status, d_steps)
         t = t.numpy().reshape(height, width)
         nrm = np.ascontiguousarray(nrm.numpy().T).reshape(height, width, 3) if normals else None
     status = status.reshape(height, width)
@@ -593,26 +608,16 @@ def spans(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=
           max_crossings=8, resident=False):
     """Every crossing of arbitrary rays with the solid of `geometry`, and their chords. `origins`, `directions` as for
     cast(). -> RaySpans. See the module text for the rule, the floor of `eps`, `lipschitz` and the refusals."""
-    t_min, t_max, eps, cone, max_steps, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
-    low, first = lower(geometry)
-    bound = _bound(low, first, lipschitz)
-    n = _check_rays(origins, directions)
-    prog = _program(low)
-    _engine.require_gpu()
-    L = _engine.lib()
-    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
-    vp = _engine._vp
+    *options, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
+    t_min, t_max = options[:2]
+    low, inv = _lowered(geometry, lipschitz)
+    n = _check_rays(origins, directions)                        # (before anything asks for the GPU)
+    prog = _on_device(low)
     with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
-        co = stack.enter_context(device_coords(origins, "render"))
-        cd = stack.enter_context(device_coords(directions, "render"))
+        source = stack.enter_context(_source(rays=(origins, directions, n)))
         chord, cross, d_count, d_status, d_steps = _span_outputs(on_error, stack, n, k)
-        d_x, xstride = _cross_args(cross)
-        _engine.check(L.sdfk_span_rays_device(prog.handle, vp(co.ptr), co.stride, vp(cd.ptr), cd.stride, n, t_min, t_max, eps,
-                                              cone, float(np.float32(1.0 / bound)), max_steps, vp(chord.ptr), d_count.at(),
-                                              d_status.at(), d_steps.at(), d_x, xstride, k, None, config.mode),
-                      "sdfk_span_rays_device")
-        _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = _small(n, d_status, d_steps)
+        status, steps = _march("sdfk_span_rays_device", prog, source, options, inv,
+                               (chord.at(), d_count.at(), d_status.at(), d_steps.at()) + _rows(cross) + (k,), n, d_status, d_steps)
         count = d_count.download(np.empty(n, dtype=np.int32))
         if resident:
             on_error.pop_all()
@@ -633,25 +638,15 @@ def thickness(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps
         floor = SPAN_EPS_FLOOR * max(abs(float(t_min)), abs(float(t_max)))
         eps = max(fe, float(np.nextafter(np.float32(floor), np.float32(np.inf)))) if np.isfinite(floor) else fe
     cone = fc if cone is None else cone
-    t_min, t_max, eps, cone, max_steps, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
-    low, first = lower(geometry)
-    bound = _bound(low, first, lipschitz)
-    prog = _program(low)
-    _engine.require_gpu()
-    L = _engine.lib()
-    _engine.check(L.sdfk_set_device(config.device), "sdfk_set_device")
-    vp = _engine._vp
-    n = width * height
-    rec = camera.record(width, height)
+    *options, k = _span_options(t_min, t_max, eps, cone, max_steps, max_crossings)
+    t_min, t_max, eps, cone = options[:4]
+    prog, inv = _setup(geometry, lipschitz)
     with contextlib.ExitStack() as stack:
+        source = stack.enter_context(_source(camera=camera, size=(width, height)))
+        n = width * height
         chord, cross, d_count, d_status, d_steps = _span_outputs(stack, stack, n, k)
-        d_x, xstride = _cross_args(cross)
-        _engine.check(L.sdfk_span_camera_device(prog.handle, _engine._ptr(rec), width, height, 1 if camera.ortho else 0, t_min,
-                                                t_max, eps, cone, float(np.float32(1.0 / bound)), max_steps, vp(chord.ptr),
-                                                d_count.at(), d_status.at(), d_steps.at(), d_x, xstride, k, None, config.mode),
-                      "sdfk_span_camera_device")
-        _engine.check(L.sdfk_sync(None), "sdfk_sync")
-        status, steps = _small(n, d_status, d_steps)
+        status, steps = _march("sdfk_span_camera_device", prog, source, options, inv,
+                               (chord.at(), d_count.at(), d_status.at(), d_steps.at()) + _rows(cross) + (k,), n, d_status, d_steps)
         count = d_count.download(np.empty(n, dtype=np.int32))
         chord = chord.numpy().reshape(height, width)
         crossings = cross.download_rows().reshape(k, height, width) if k else None

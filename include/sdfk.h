@@ -102,7 +102,9 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
 #define SDFK_FLAVOUR_ROWS2D_GRID 9
 #define SDFK_FLAVOUR_RAYS 10       /* sdfk_spec_rays / sdfk_spec_raycam: sphere tracing (sdfk_trace_rays_device /
                                       sdfk_trace_camera_device) around the straight-line body, one ray per lane; needs no
-                                      cull sites and has no FLAGS / XY build. Not part of sdfk_program_compile_check. */
+                                      cull sites and has no FLAGS / XY build. Not part of sdfk_program_compile_check. The
+                                      kernels of RAYS and SPANS take (PRM, TAB, source, options, the march's outputs, STATS):
+                                      csrc/sdfk_raydev.h, SDFK_MARCH_KERNEL; long chains get a culled pair (csrc/sdfk_raycull.h). */
 #define SDFK_FLAVOUR_OCCUPANCY 11  /* sdfk_spec_occ_list / sdfk_spec_occ_all: the sample pass of sdfk_eval_grid_occupancy around
                                       the same body, one sub-sample per lane; as RAYS: no cull sites needed, no FLAGS / XY
                                       build, not part of sdfk_program_compile_check. */

@@ -1,4 +1,4 @@
-"""The culled ray kernels of long hard unions (per-wave survivor lists: csrc/sdfk_codegen.cpp kRaysCull) on
+"""The culled ray kernels of long hard unions (per-wave survivor lists: csrc/sdfk_raycull.h SdfkCullField) on
 the GPU: the same bits as the plain kernel (MODE_NOCULL) over scenes, views and the edge cases of cast; the lists exist and
 are used (statistics build); soundness and parity of the 1000-member union against the float64 tracer."""
 import ctypes

@@ -1,4 +1,4 @@
-"""A numpy model of the per-wave survivor lists of the culled ray kernels (csrc/sdfk_codegen.cpp, kRaysCull):
+"""A numpy model of the per-wave survivor lists of the culled ray kernels (csrc/sdfk_raycull.h, SdfkCullField):
 what the rule costs in member evaluations, in float64 on the CPU. It predicts counts, not time.
 
     python tools/ray_cull_model.py [--members 1000 --width 320 --height 240 --cap 192 --depth 3 --look 0 --tiles 150]
