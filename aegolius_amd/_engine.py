@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsdfk.so")
 MODE_AUTO, MODE_INTERPRET, MODE_SPECIALIZED, MODE_NOCULL = 0, 1, 2, 3
 (FLAVOUR_PLAIN_ARRAY, FLAVOUR_PLAIN_GRID, FLAVOUR_TILE_ARRAY, FLAVOUR_TILE_GRID, FLAVOUR_TILE_MASK, FLAVOUR_ROWS_ARRAY,
  FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID, FLAVOUR_RAYS, FLAVOUR_OCCUPANCY,
- FLAVOUR_SPANS) = range(13)
+ FLAVOUR_SPANS, FLAVOUR_SECONDARY) = range(14)
 FLAVOUR_FLAGS = 0x100      # OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (fused selection)
 FLAVOUR_XY = 0x200         # OR-ed onto PLAIN_ARRAY / ROWS2D_ARRAY: the build for two-row coordinates (z = 0 by contract)
 
@@ -142,6 +142,10 @@ SIGNATURES = {
                                      _c.c_float, _int, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _int]),
     "sdfk_span_camera_device": (_int, [_vp, _vp, _int, _int, _int, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                        _c.c_float, _int, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _int]),
+    "sdfk_visibility_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
+                                           _c.c_float, _int, _c.c_float, _vp, _vp, _vp, _vp, _vp, _int]),
+    "sdfk_occlusion_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _int, _c.c_float, _c.c_float, _vp, _vp,
+                                          _int]),
     "sdfk_eval_grid_occupancy_scratch": (_sz, [_i64, _i64, _i64, _i64]),
     "sdfk_eval_grid_occupancy": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float,
                                         _c.c_float, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64), _fp, _vp, _int]),

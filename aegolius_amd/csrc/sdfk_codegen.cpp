@@ -116,6 +116,16 @@ static const char kSpansCullKernels[] = R"SDFKW(
 SDFK_MARCH_KERNEL(sdfk_spec_spans_cull, SDFK_ARRAY, SDFK_SPAN, SDFK_FIELD_CULL)
 SDFK_MARCH_KERNEL(sdfk_spec_spancam_cull, SDFK_CAMERA, SDFK_SPAN, SDFK_FIELD_CULL)
 )SDFKW";
+// The secondary marches (SDFK_FL_SECONDARY): visibility and ambient occlusion, both over array rays — a secondary ray
+// starts on a surface, never at a camera.
+static const char kSecondary[] = R"SDFKW(
+SDFK_MARCH_KERNEL(sdfk_spec_visibility, SDFK_ARRAY, SDFK_VIS, SDFK_FIELD_PLAIN)
+SDFK_MARCH_KERNEL(sdfk_spec_occlusion, SDFK_ARRAY, SDFK_AO, SDFK_FIELD_PLAIN)
+)SDFKW";
+static const char kSecondaryCullKernels[] = R"SDFKW(
+SDFK_MARCH_KERNEL(sdfk_spec_visibility_cull, SDFK_ARRAY, SDFK_VIS, SDFK_FIELD_CULL)
+SDFK_MARCH_KERNEL(sdfk_spec_occlusion_cull, SDFK_ARRAY, SDFK_AO, SDFK_FIELD_CULL)
+)SDFKW";
 
 // Sub-voxel occupancy (SDFK_FL_OCCUPANCY): the sample pass of sdfk_occdev.h around the same field object as the plain ray
 // kernels, over a list of cells or over all cells of a slab; the same text as the interpreter sample kernel
@@ -2533,7 +2543,7 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
     g.s += "\n";
     g.s += kEmbeddedAccess;
     char buf[64];
-    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY || flavour == SDFK_FL_SPANS) {
+    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY || flavour == SDFK_FL_SPANS || flavour == SDFK_FL_SECONDARY) {
         // Sphere tracing: the plain body, one ray per lane (scalar T: lanes diverge per ray, and two rays per lane would
         // double every wave's tail), inside the marching loop of sdfk_raydev.h. A long hard union that the field kernels
         // run table-driven ("chain mode") keeps its table-driven plain body, which builds in a second whatever the number
@@ -2564,13 +2574,14 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
         }
         g.s += kEmbeddedRaydev;
         g.s += kSpecField;
-        g.s += flavour == SDFK_FL_SPANS ? kSpans : kRays;     // (the span flavour: the same field objects, the other march)
+        // (the span and the secondary flavours: the same field objects, the other marches)
+        g.s += flavour == SDFK_FL_SPANS ? kSpans : flavour == SDFK_FL_SECONDARY ? kSecondary : kRays;
         if (chain) {
             g.s += "\n#ifndef SDFK_RAYS_CULL_MIN_LEAVES\n#define SDFK_RAYS_CULL_MIN_LEAVES 64    // (measured: DESIGN 4.14 has the table)\n#endif\n"
                    "#if SDFK_NLEAF >= SDFK_RAYS_CULL_MIN_LEAVES\n";
             g.s += kWaveHelpers;
             g.s += kEmbeddedRaycull;
-            g.s += flavour == SDFK_FL_SPANS ? kSpansCullKernels : kRaysCullKernels;
+            g.s += flavour == SDFK_FL_SPANS ? kSpansCullKernels : flavour == SDFK_FL_SECONDARY ? kSecondaryCullKernels : kRaysCullKernels;
             g.s += "#endif\n";
         }
         return g.s;

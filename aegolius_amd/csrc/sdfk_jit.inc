@@ -404,7 +404,14 @@ static const char* const kFlavourFn[SDFK_FL_COUNT][2] = {
     {"sdfk_spec_v4", "sdfk_spec_v1"}, {"sdfk_spec_g4", "sdfk_spec_g1"}, {"sdfk_spec_t", nullptr}, {"sdfk_spec_tg", nullptr},
     {"sdfk_spec_tmask", nullptr},     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr}, {"sdfk_spec_rmask", nullptr},
     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr},        {"sdfk_spec_rays", "sdfk_spec_raycam"},
-    {"sdfk_spec_occ_list", "sdfk_spec_occ_all"},                        {"sdfk_spec_spans", "sdfk_spec_spancam"}};
+    {"sdfk_spec_occ_list", "sdfk_spec_occ_all"},                        {"sdfk_spec_spans", "sdfk_spec_spancam"},
+    {"sdfk_spec_visibility", "sdfk_spec_occlusion"}};
+// the march flavours: built by the first call that needs them, from programs with or without cull sites, one build each
+static bool march_flavour(int f) { return f == SDFK_FL_RAYS || f == SDFK_FL_SPANS || f == SDFK_FL_SECONDARY; }
+// ... and the second pair of kernels that long chains get in them (culling along the rays, sdfk_raycull.h): fn[2], fn[3]
+static const char* const kMarchCullFn[3][2] = {{"sdfk_spec_rays_cull", "sdfk_spec_raycam_cull"},
+                                               {"sdfk_spec_spans_cull", "sdfk_spec_spancam_cull"},
+                                               {"sdfk_spec_visibility_cull", "sdfk_spec_occlusion_cull"}};
 
 // hiprtc is entered by ONE thread at a time, and never while a code object is being loaded (hipModuleLoadData):
 // g_rtc_mu. Background builds are queued to one worker thread, which is drained before the interpreter / the
@@ -549,9 +556,8 @@ extern "C" int sdfk_program_compile_check(sdfk_program* p, size_t* code_size) {
     size_t total = 0;
     const int rwb = rows_geo(p);
     for (int f = 0; f < SDFK_FL_COUNT; ++f) {
-        if (f == SDFK_FL_RAYS) continue;                        // (not an evaluation flavour: built by the first ray cast)
+        if (march_flavour(f)) continue;                         // (not evaluation flavours: built by the first cast / span / secondary call)
         if (f == SDFK_FL_OCCUPANCY) continue;                   // (nor this one: built by the first occupancy call)
-        if (f == SDFK_FL_SPANS) continue;                       // (nor this one: built by the first span call)
         if (p->sites.empty() && f != SDFK_FL_PLAIN_ARRAY && f != SDFK_FL_PLAIN_GRID) continue;
         if (p->chain_mode && (f == SDFK_FL_TILE_ARRAY || f == SDFK_FL_TILE_GRID || f == SDFK_FL_TILE_MASK || f == SDFK_FL_ROWS_MASK)) continue;
         std::shared_ptr<CodeObject> e = code_get(flavour_key(p, f, rwb), [&] { return flavour_source(p, f); }, rwb, true);
@@ -569,8 +575,8 @@ extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t
     if (flavour >= 0 && (flavour & SDFK_FLAVOUR_XY)) with_flags |= 2;                // two-row coordinates
     if (flavour >= 0) flavour &= ~(SDFK_FLAVOUR_FLAGS | SDFK_FLAVOUR_XY);
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_program_compile_flavour: unknown flavour");
-    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_SPANS)
+    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && !march_flavour(flavour) &&
+        flavour != SDFK_FL_OCCUPANCY)
         return fail(-2, "sdfk_program_compile_flavour: the program has no cull sites");
     if (with_flags && flavour == SDFK_FL_RAYS)
         return fail(-2, "sdfk_program_compile_flavour: the ray flavour has no flag-writing or two-row build");
@@ -578,6 +584,8 @@ extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t
         return fail(-2, "sdfk_program_compile_flavour: the occupancy flavour has no flag-writing or two-row build");
     if (with_flags && flavour == SDFK_FL_SPANS)
         return fail(-2, "sdfk_program_compile_flavour: the span flavour has no flag-writing or two-row build");
+    if (with_flags && flavour == SDFK_FL_SECONDARY)
+        return fail(-2, "sdfk_program_compile_flavour: the secondary flavour has no flag-writing or two-row build");
     if ((with_flags & 2) && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_ROWS2D_ARRAY)
         return fail(-2, "sdfk_program_compile_flavour: two-row coordinates exist for the plain and the flat row-block array kernels");
     if ((with_flags & 1) && (flavour == SDFK_FL_TILE_ARRAY || flavour == SDFK_FL_TILE_GRID || flavour == SDFK_FL_TILE_MASK ||
@@ -597,8 +605,8 @@ extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t
 extern "C" int sdfk_debug_compile_external(sdfk_program* p, int flavour, size_t* code_size) {
     if (!p) return fail(-1, "null program");
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_debug_compile_external: unknown flavour");
-    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && flavour != SDFK_FL_RAYS &&
-        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_SPANS)
+    if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && !march_flavour(flavour) &&
+        flavour != SDFK_FL_OCCUPANCY)
         return fail(-2, "sdfk_debug_compile_external: the program has no cull sites");
     if (!rtc_helper_available()) return fail(-9, "sdfk_rtc_helper is not next to libsdfk.so (or hiprtc cannot be located)");
     std::vector<char> co;
@@ -663,17 +671,11 @@ static std::shared_ptr<SpecModule> get_module(sdfk_program* p, int device, int f
                 (void)hipGetLastError();
             }
         }
-        if (he == hipSuccess && flavour == SDFK_FL_RAYS) {
-            // long chains come with a second pair of kernels that cull along the rays (sdfk_raycull.h)
-            if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_rays_cull") != hipSuccess ||
-                hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_raycam_cull") != hipSuccess) {
-                m->fn[2] = m->fn[3] = nullptr;
-                (void)hipGetLastError();
-            }
-        }
-        if (he == hipSuccess && flavour == SDFK_FL_SPANS) {     // (likewise: SdfkCullField inside the span march)
-            if (hipModuleGetFunction(&m->fn[2], m->mod, "sdfk_spec_spans_cull") != hipSuccess ||
-                hipModuleGetFunction(&m->fn[3], m->mod, "sdfk_spec_spancam_cull") != hipSuccess) {
+        if (he == hipSuccess && march_flavour(flavour)) {
+            // long chains come with a second pair of kernels that cull along the rays (SdfkCullField inside the same march)
+            const char* const* cull = kMarchCullFn[flavour == SDFK_FL_RAYS ? 0 : flavour == SDFK_FL_SPANS ? 1 : 2];
+            if (hipModuleGetFunction(&m->fn[2], m->mod, cull[0]) != hipSuccess ||
+                hipModuleGetFunction(&m->fn[3], m->mod, cull[1]) != hipSuccess) {
                 m->fn[2] = m->fn[3] = nullptr;
                 (void)hipGetLastError();
             }

@@ -1,8 +1,10 @@
 // sdfk_raydev.h — sphere tracing of one program: the marching loops, the ray sources and the stencil normals. Shared
 // (like sdfk_access.h) by the interpreter march kernel (sdfk_rays.inc) and, as embedded text, by the hiprtc-specialised
-// ones (SDFK_FL_RAYS, SDFK_FL_SPANS), so that the marching arithmetic is ONE piece of text: both kernels give the same bits.
+// ones (SDFK_FL_RAYS, SDFK_FL_SPANS, SDFK_FL_SECONDARY), so that the marching arithmetic is ONE piece of text: both kernels give the same bits.
 // One interface for every march: sdfk_march(src, field, opts, out), overloaded on the output record — SdfkHitOut: the first
-// hit (sdfk_trace, the rule below), SdfkSpanOut: every crossing and the chord (sdfk_trace_spans, the rule further down).
+// hit (sdfk_trace, the rule below), SdfkSpanOut: every crossing and the chord (sdfk_trace_spans, the rule further down),
+// SdfkVisOut: how much of a segment is free of the solid (sdfk_trace_visibility), SdfkAoOut: how open the half-space above
+// a surface point is (sdfk_trace_occlusion) — the two secondary marches, at the end of this file.
 //
 // The marching rule (aegolius_amd/render.py states it for users; tests/render_reference.py is its float64 copy):
 //     t = t_min
@@ -72,6 +74,19 @@ struct SdfkSpanOut {        // spans: length inside the solid, all crossings cou
     float* __restrict__ cross;  // the first max_crossings crossings, rows cstride apart (not read when max_crossings is 0)
     long long cstride;
     int max_crossings;
+};
+struct SdfkVisOut {         // visibility: what the ray saw of the light in [0, 1], 0 clear / 1 blocked / 2 step limit, advances made
+    float softness;         // k of the penumbra estimate; 0: hard, vis is 0 or 1
+    const float* __restrict__ limits;   // the end of every ray (a point light's distance), t_max where that is smaller; null: t_max
+    float* __restrict__ vis;
+    unsigned char* __restrict__ status;
+    int* __restrict__ steps;
+};
+#define SDFK_AO_MAX_SAMPLES 16
+struct SdfkAoOut {          // ambient occlusion of the points `o` with the unit normals `d` of the source
+    float inv_m, inv_radius;    // 1 / samples and 1 / radius rounded to fp32 on the host (radius: opts.t_max, samples: opts.max_steps)
+    float strength;
+    float* __restrict__ ao;
 };
 
 // -> is there a ray on this lane; its origin, direction and the index its results are stored at
@@ -280,6 +295,97 @@ static __device__ __forceinline__ void sdfk_trace_spans(const SRC& src, const FI
     }
 }
 
+// ---- secondary marches: what a surface point sees ------------------------------------------------------------------------------
+// Visibility of a segment (aegolius_amd/render.py states the rule for users; tests/secondary_reference.py is its float64
+// copy), per ray, in fp32:
+//     t = t_min; vis = 1; t_end = limits ? min(t_max, limits[i]) : t_max
+//     repeat at most max_steps times:
+//         f   = field(o + t d)                           fmaf(t, d, o) per component, as above
+//         thr = max(eps, cone t)
+//         if f <= thr: vis = 0; status = HIT; stop       blocked
+//         if k > 0: vis = min(vis, k (f / L) / t)        the penumbra estimate; t = 0 gives +inf, since f > thr >= 0
+//         t   = fmaf(f, 1 / L, t); steps += 1
+//         if t > t_end: status = MISS; stop              clear
+//     otherwise: status = LIMIT                          vis is what was seen so far, never folded into 0 or 1
+// The advance, the hit test and the miss test are sdfk_trace's: with limits null, status, steps and the final t are those
+// of the first-hit march, whatever k. f / L is the radius of a ball around o + t d that is free of the solid, so
+// k (f / L) / t compares the angular size of the free cone around the ray with 1 / k: a ray that passes closer to the solid
+// than t / k anywhere sees less than the whole light. t_min >= 0 (the entry point's check) keeps vis in [0, 1] without a
+// clamp. The shape is sdfk_trace's: the loop runs while any lane marches, the hook is called before the one evaluation,
+// finished lanes evaluate along, masked.
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_trace_visibility(const SRC& src, const FIELD& field, const sdfk_rayopts R,
+                                                             const float softness, const float* __restrict__ limits,
+                                                             float* __restrict__ out_vis, unsigned char* __restrict__ out_status,
+                                                             int* __restrict__ out_steps) {
+    V3 o, d;
+    long long at;
+    const bool live = sdfk_ray_load(src, o, d, at);
+    float t_end = R.t_max;
+    if (limits && live) t_end = fminf(R.t_max, limits[at]);    // (limits: wave-uniform, a kernel argument)
+    float t = R.t_min, vis = 1.0f;
+    unsigned status = SDFK_RAY_LIMIT;
+    int steps = 0;
+    bool marching = live;
+    for (int it = 0; it < R.max_steps; ++it) {
+        if (!__any(marching)) break;
+        const V3 p = {fmaf(t, d.x, o.x), fmaf(t, d.y, o.y), fmaf(t, d.z, o.z)};
+        field.prepare(p, t, marching, 0.0f);
+        const float f = field(p);
+        if (marching) {
+            const float thr = fmaxf(R.eps, R.cone * t);
+            if (f <= thr) {
+                vis = 0.0f;
+                status = SDFK_RAY_HIT;
+                marching = false;
+            } else {
+                if (softness > 0.0f) vis = fminf(vis, softness * (f * R.inv_lip) / t);
+                t = fmaf(f, R.inv_lip, t);
+                ++steps;
+                if (t > t_end) {
+                    status = SDFK_RAY_MISS;
+                    marching = false;
+                }
+            }
+        }
+    }
+    if (live) {
+        out_vis[at] = vis;
+        out_status[at] = (unsigned char)status;
+        out_steps[at] = steps;
+    }
+}
+
+// Ambient occlusion of a surface point p with the unit normal n (the source's o and d), m = samples, in fp32:
+//     occ = 0
+//     for i = 1 .. m:
+//         h   = radius (float)i (1 / m)                  1 / m rounded once on the host
+//         f   = field(p + h n)                           fmaf(h, n, p) per component
+//         occ = fmaf(2^-i, max(0, h - f / L), occ)       f * (1 / L), 1 / L rounded once on the host
+//     ao = min(1, max(0, 1 - strength occ (1 / radius)))       1 / radius rounded once on the host
+// Above a plane f / L = h at every sample and ao = 1; whatever else comes within h of the sample lowers f and darkens the
+// point, near samples counting most. Every lane has the same trip count, so the loop needs no ballot: the hook is called
+// with the lanes that hold a point, before the one evaluation (a wave without a point does nothing at all).
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_trace_occlusion(const SRC& src, const FIELD& field, const sdfk_rayopts R,
+                                                            const float inv_m, const float inv_radius, const float strength,
+                                                            float* __restrict__ out_ao) {
+    V3 p, n;
+    long long at;
+    const bool live = sdfk_ray_load(src, p, n, at);
+    if (!__any(live)) return;
+    float occ = 0.0f, w = 1.0f;
+    _Pragma("unroll 1") for (int i = 1; i <= R.max_steps; ++i) {    // (one call site of the field)
+        const float h = R.t_max * (float)i * inv_m;
+        const V3 q = {fmaf(h, n.x, p.x), fmaf(h, n.y, p.y), fmaf(h, n.z, p.z)};
+        field.prepare(q, h, live, 0.0f);
+        const float f = field(q);
+        w *= 0.5f;                                                  // 2^-i, exact
+        occ = fmaf(w, fmaxf(0.0f, h - f * R.inv_lip), occ);
+    }
+    if (live) out_ao[at] = fminf(1.0f, fmaxf(0.0f, 1.0f - strength * occ * inv_radius));
+}
+
 // The one interface of the marches: the output record selects the loop.
 template <typename SRC, typename FIELD>
 static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkHitOut out) {
@@ -289,8 +395,16 @@ template <typename SRC, typename FIELD>
 static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkSpanOut out) {
     sdfk_trace_spans(src, field, R, out.max_crossings, out.chord, out.count, out.status, out.steps, out.cross, out.cstride);
 }
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkVisOut out) {
+    sdfk_trace_visibility(src, field, R, out.softness, out.limits, out.vis, out.status, out.steps);
+}
+template <typename SRC, typename FIELD>
+static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& field, const sdfk_rayopts R, const SdfkAoOut out) {
+    sdfk_trace_occlusion(src, field, R, out.inv_m, out.inv_radius, out.strength, out.ao);
+}
 
-// One specialised kernel of the generated text: NAME runs the march OUT (SDFK_HIT or SDFK_SPAN) on the rays of SRC
+// One specialised kernel of the generated text: NAME runs the march OUT (SDFK_HIT, SDFK_SPAN, SDFK_VIS or SDFK_AO) on the rays of SRC
 // (SDFK_ARRAY: SdfkRaysArray; SDFK_CAMERA: the camera record, wrapped into SdfkRaysCamera) around FIELD (SDFK_FIELD_PLAIN,
 // or SDFK_FIELD_CULL of sdfk_raycull.h). Parameters: (PRM, TAB, the source, opts, the march's outputs, STATS) — STATS: the
 // counters of the statistics build of the culled first-hit kernels, null in every other launch. The outputs are flat
@@ -309,6 +423,12 @@ static __device__ __forceinline__ void sdfk_march(const SRC& src, const FIELD& f
         long long cstride
 #define SDFK_SPAN_MARCH \
     sdfk_trace_spans(src, field, opts, max_crossings, out_chord, out_count, out_status, out_steps, out_cross, cstride)
+#define SDFK_VIS_PARAMS                                                                                           \
+    float softness, const float *__restrict__ limits, float *__restrict__ out_vis,                                \
+        unsigned char *__restrict__ out_status, int *__restrict__ out_steps
+#define SDFK_VIS_MARCH sdfk_trace_visibility(src, field, opts, softness, limits, out_vis, out_status, out_steps)
+#define SDFK_AO_PARAMS float inv_m, float inv_radius, float strength, float *__restrict__ out_ao
+#define SDFK_AO_MARCH sdfk_trace_occlusion(src, field, opts, inv_m, inv_radius, strength, out_ao)
 #define SDFK_FIELD_PLAIN const SdfkSpecField field = {PRM, TAB}
 #define SDFK_MARCH_KERNEL(NAME, SRC, OUT, FIELD)                                                                   \
     extern "C" __global__ __launch_bounds__(SDFK_RAY_BLOCK) void NAME(const float* __restrict__ PRM,              \

@@ -2,17 +2,18 @@
 //
 //   * sdfk_march_interp_kernel<NC, NV, SRC, OUT> : the interpreter's register machine as a __device__ evaluation of ONE
 //     point (SdfkInterpField, sdfk_interpfield.h) called from the marching loop that OUT selects: SdfkHitOut the first hit,
-//     SdfkSpanOut the march that goes on through the surface (every crossing, the chord). One ray per lane; the code words
+//     SdfkSpanOut the march that goes on through the surface (every crossing, the chord), SdfkVisOut the visibility of a
+//     segment and SdfkAoOut ambient occlusion (the secondary marches: array rays only). One ray per lane; the code words
 //     are wave-uniform (scalar loads) because the loop's trip count is. SRC = SdfkRaysArray (two (3, n) arrays) or
 //     SdfkRaysCamera (rays generated from the camera record, one 8 x 8 pixel tile per wave). Register files as in
 //     sdfk_interp_kernel, and with the same outcome as its one-point-per-lane instantiations (compiler's resource remarks,
 //     all four first-hit instances: 57 VGPRs, 8 waves per SIMD): the small coordinate file stays in VGPRs and its three
 //     value registers, indexed by the wave-uniform operand fields, take 16 bytes of scratch per lane
 //     (sdfk_interp_kernel<1, 2, 3>: 16 as well); the full file takes 128.
-//   * the specialised flavours (SDFK_FL_RAYS, SDFK_FL_SPANS, sdfk_codegen.cpp) wrap the generated sdfk_point<float> in the
+//   * the specialised flavours (SDFK_FL_RAYS, SDFK_FL_SPANS, SDFK_FL_SECONDARY, sdfk_codegen.cpp) wrap the generated sdfk_point<float> in the
 //     same loops; long hard unions (chain mode) get a second pair of kernels there that folds the chain over per-wave
 //     survivor lists in LDS (sdfk_raycull.h) — what SPECIALIZED / AUTO launch, NOCULL the plain pair; same bits.
-//   * the host side is one path for both marches: an entry point fills a MarchRequest, march_run picks and launches.
+//   * the host side is one path for all marches: an entry point fills a MarchRequest, march_run picks and launches.
 // Outputs per ray, first hit: t (fp32), status (1 byte: 0 miss, 1 hit, 2 step limit), steps (int32), optionally the
 // stencil normal (three strided rows). Plain vector stores, written once; no atomics, no LDS.
 #include "sdfk_interpfield.h"
@@ -105,7 +106,7 @@ struct MarchRequest {
     std::variant<SdfkRaysArray, sdfk_camera> src;     // array rays (count = rays), or a parsed camera (count = pixels)
     long long count;
     sdfk_rayopts opts;
-    std::variant<SdfkHitOut, SdfkSpanOut> out;        // the output record, which also says which march
+    std::variant<SdfkHitOut, SdfkSpanOut, SdfkVisOut, SdfkAoOut> out;   // the output record, which also says which march
     void* stream;
     int mode;
 };
@@ -154,8 +155,53 @@ static int span_outputs(const char* who, float* d_chord, int* d_count, unsigned 
     return 0;
 }
 
-// The program's check, the kernel that serves the call (pick_kernel) and its launch. The two marches differ in the flavour,
-// in pick_kernel's text and in the counters of the statistics build, which only the culled first-hit kernels feed.
+static int vis_outputs(const char* who, float softness, const float* d_limits, float* d_vis, unsigned char* d_status,
+                       int* d_steps, SdfkVisOut* out) {
+    const std::string w = who;
+    if (!std::isfinite(softness) || !(softness >= 0.0f)) return fail(-1, w + ": softness must be finite and not negative");
+    if (!d_vis || !d_status || !d_steps) return fail(-1, w + ": null output pointer");
+    *out = {softness, d_limits, d_vis, d_status, d_steps};
+    return 0;
+}
+
+// What march_run asks of an output record: the flavour that holds its kernels and its name in messages, which of the
+// flavour's two kernels runs it (first hit and spans: the camera one; the secondary flavour: the occlusion one), whether
+// the march has a camera source at all, and its kernel arguments in the order of its SDFK_*_PARAMS.
+struct MarchKind {
+    int flavour;
+    const char* what;
+    bool second, camera;
+};
+static MarchKind march_kind(const SdfkHitOut&, bool cam) { return {SDFK_FL_RAYS, "ray kernel", cam, true}; }
+static MarchKind march_kind(const SdfkSpanOut&, bool cam) { return {SDFK_FL_SPANS, "span kernel", cam, true}; }
+static MarchKind march_kind(const SdfkVisOut&, bool) { return {SDFK_FL_SECONDARY, "visibility kernel", false, false}; }
+static MarchKind march_kind(const SdfkAoOut&, bool) { return {SDFK_FL_SECONDARY, "occlusion kernel", true, false}; }
+static int march_args(SdfkHitOut& h, void** a) {
+    int n = 0;
+    for (void* x : {(void*)&h.t, (void*)&h.status, (void*)&h.steps, (void*)&h.n, (void*)&h.nstride}) a[n++] = x;
+    return n;
+}
+static int march_args(SdfkSpanOut& s, void** a) {
+    int n = 0;
+    for (void* x : {(void*)&s.max_crossings, (void*)&s.chord, (void*)&s.count, (void*)&s.status, (void*)&s.steps, (void*)&s.cross,
+                    (void*)&s.cstride})
+        a[n++] = x;
+    return n;
+}
+static int march_args(SdfkVisOut& v, void** a) {
+    int n = 0;
+    for (void* x : {(void*)&v.softness, (void*)&v.limits, (void*)&v.vis, (void*)&v.status, (void*)&v.steps}) a[n++] = x;
+    return n;
+}
+static int march_args(SdfkAoOut& o, void** a) {
+    int n = 0;
+    for (void* x : {(void*)&o.inv_m, (void*)&o.inv_radius, (void*)&o.strength, (void*)&o.ao}) a[n++] = x;
+    return n;
+}
+
+// The program's check, the kernel that serves the call (pick_kernel) and its launch. The marches differ in what march_kind
+// says of their record, in their kernel arguments and in the counters of the statistics build, which only the culled
+// first-hit kernels feed.
 static int march_run(const MarchRequest& r) {
     int bad = -1;
     const int chk = sdfk_program_rays_check(r.p, &bad);
@@ -167,7 +213,8 @@ static int march_run(const MarchRequest& r) {
     if (rc) return rc;
     hipStream_t stream = x.stream;
     const sdfk_camera* cam = std::get_if<sdfk_camera>(&r.src);
-    const bool spans = std::holds_alternative<SdfkSpanOut>(r.out);
+    const MarchKind kind = std::visit([&](const auto& o) { return march_kind(o, cam != nullptr); }, r.out);
+    if (cam && !kind.camera) return fail(-1, std::string(r.who) + ": this march has no camera source");
     unsigned blocks;
     if (cam) {
         const long long tiles = (long long)((cam->width + 7) / 8) * ((cam->height + 7) / 8);
@@ -176,8 +223,7 @@ static int march_run(const MarchRequest& r) {
         blocks = (unsigned)((r.count + SDFK_RAY_BLOCK - 1) / SDFK_RAY_BLOCK);
     }
     std::shared_ptr<SpecModule> sk;                            // (a failed build falls back in AUTO only)
-    rc = pick_kernel(r.p, x.device, spans ? SDFK_FL_SPANS : SDFK_FL_RAYS, 0, mode, mode == SDFK_MODE_AUTO,
-                     spans ? "span kernel" : "ray kernel", false, &sk);
+    rc = pick_kernel(r.p, x.device, kind.flavour, 0, mode, mode == SDFK_MODE_AUTO, kind.what, false, &sk);
     if (rc) return rc;
     const float* prm = x.prm;
     const float* tab = x.tab;
@@ -185,26 +231,19 @@ static int march_run(const MarchRequest& r) {
         // the culled pair (long chains only) unless the caller asked for the kernel without culling
         const bool cull = mode != SDFK_MODE_NOCULL && sk->fn[2] && sk->fn[3];
         unsigned long long* stats = nullptr;
-        if (cull && !spans && g_rays_stats_on.load()) {
+        if (cull && kind.flavour == SDFK_FL_RAYS && g_rays_stats_on.load()) {
             rc = rays_stats_buffer(&stats, stream);
             if (rc) return rc;
         }
-        // (PRM, TAB, source, opts, the march's outputs in the order of SDFK_HIT_PARAMS / SDFK_SPAN_PARAMS, STATS)
+        // (PRM, TAB, source, opts, the march's outputs in the order of its SDFK_*_PARAMS, STATS)
         auto src = r.src;
         auto out = r.out;
         sdfk_rayopts opts = r.opts;
         void* args[12] = {&prm, &tab, std::visit([](auto& s) { return (void*)&s; }, src), &opts};
         int n = 4;
-        if (SdfkSpanOut* s = std::get_if<SdfkSpanOut>(&out)) {
-            for (void* a : {(void*)&s->max_crossings, (void*)&s->chord, (void*)&s->count, (void*)&s->status, (void*)&s->steps,
-                            (void*)&s->cross, (void*)&s->cstride})
-                args[n++] = a;
-        } else {
-            SdfkHitOut* h = std::get_if<SdfkHitOut>(&out);
-            for (void* a : {(void*)&h->t, (void*)&h->status, (void*)&h->steps, (void*)&h->n, (void*)&h->nstride}) args[n++] = a;
-        }
+        n += std::visit([&](auto& o) { return march_args(o, args + n); }, out);
         args[n++] = &stats;
-        HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (cam ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
+        HIPCHK(hipModuleLaunchKernel(sk->fn[(cull ? 2 : 0) + (kind.second ? 1 : 0)], blocks, 1, 1, SDFK_RAY_BLOCK, 1, 1, 0, stream, args,
                                      nullptr));
         if (stats) {
             rc = rays_stats_collect(stats, stream);
@@ -221,8 +260,14 @@ static int march_run(const MarchRequest& r) {
 #undef SDFK_MARCH_GO
     };
     std::visit([&](auto out) {
-        if (cam) launch(SdfkRaysCamera{*cam}, out);
-        else launch(std::get<SdfkRaysArray>(r.src), out);
+        // (a march without a camera source has no camera instance of the interpreter kernel either)
+        if constexpr (std::is_same_v<decltype(out), SdfkHitOut> || std::is_same_v<decltype(out), SdfkSpanOut>) {
+            if (cam) {
+                launch(SdfkRaysCamera{*cam}, out);
+                return;
+            }
+        }
+        launch(std::get<SdfkRaysArray>(r.src), out);
     }, r.out);
     HIPCHK(hipGetLastError());
     return 0;
@@ -277,4 +322,39 @@ extern "C" int sdfk_span_camera_device(sdfk_program* p, const float* camera, int
     if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
     if (!rc) rc = span_outputs(r.who, d_chord, d_count, d_status, d_steps, d_crossings, crossing_stride, max_crossings, r.count, &std::get<SdfkSpanOut>(r.out));
     return rc ? rc : march_run(r);
+}
+
+// ---- the secondary marches: array rays only ------------------------------------------------------------------------------------
+extern "C" int sdfk_visibility_rays_device(sdfk_program* p, const float* d_origins, int64_t origin_stride,
+                                           const float* d_directions, int64_t direction_stride, int64_t n, float t_min,
+                                           float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float softness,
+                                           const float* d_limits, float* d_vis, unsigned char* d_status, int* d_steps,
+                                           void* stream, int mode) {
+    if (!p) return fail(-1, "null program");
+    MarchRequest r = {"sdfk_visibility_rays_device", p, SdfkRaysArray{}, (long long)n, {}, SdfkVisOut{}, stream, mode};
+    int rc = ray_arrays(r.who, d_origins, origin_stride, d_directions, direction_stride, n, &std::get<SdfkRaysArray>(r.src));
+    if (!rc) rc = rays_options(r.who, t_min, t_max, eps, cone, inv_lipschitz, max_steps, &r.opts);
+    if (!rc && !(t_min >= 0.0f)) rc = fail(-1, std::string(r.who) + ": t_min must not be negative");
+    if (!rc) rc = vis_outputs(r.who, softness, d_limits, d_vis, d_status, d_steps, &std::get<SdfkVisOut>(r.out));
+    return rc ? rc : march_run(r);
+}
+
+extern "C" int sdfk_occlusion_rays_device(sdfk_program* p, const float* d_points, int64_t point_stride, const float* d_normals,
+                                          int64_t normal_stride, int64_t n, float radius, int samples, float strength,
+                                          float inv_lipschitz, float* d_ao, void* stream, int mode) {
+    if (!p) return fail(-1, "null program");
+    MarchRequest r = {"sdfk_occlusion_rays_device", p, SdfkRaysArray{}, (long long)n, {}, SdfkAoOut{}, stream, mode};
+    const std::string w = r.who;
+    int rc = ray_arrays(r.who, d_points, point_stride, d_normals, normal_stride, n, &std::get<SdfkRaysArray>(r.src));
+    if (rc) return rc;
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(-1, w + ": radius must be finite and positive");
+    if (samples < 1 || samples > SDFK_AO_MAX_SAMPLES)
+        return fail(-1, w + ": samples from 1 to " + std::to_string(SDFK_AO_MAX_SAMPLES));
+    if (!std::isfinite(strength) || !(strength >= 0.0f)) return fail(-1, w + ": strength must be finite and not negative");
+    // the options the loop reads: t_max = the radius, max_steps = the samples, 1 / L (t_min, eps and cone play no part)
+    rc = rays_options(r.who, 0.0f, radius, 0.0f, 0.0f, inv_lipschitz, samples, &r.opts);
+    if (rc) return rc;
+    if (!d_ao) return fail(-1, w + ": null output pointer");
+    r.out = SdfkAoOut{1.0f / (float)samples, 1.0f / radius, strength, d_ao};
+    return march_run(r);
 }

@@ -1,5 +1,6 @@
-"""Sphere tracing of geometries on the GPU: ray casts, depth / normal images, and spans — every crossing of a ray with
-the solid, chords and thickness images (kernels: csrc/sdfk_rays.inc).
+"""Sphere tracing of geometries on the GPU: ray casts, depth / normal images, spans — every crossing of a ray with
+the solid, chords and thickness images — and secondary rays: visibility of segments, soft shadows and ambient occlusion
+(kernels: csrc/sdfk_rays.inc).
 
     from aegolius_amd import render
     cam = render.Camera(eye=(2.2, 1.6, 1.9), target=(0, 0, 0), fov=40)
@@ -8,6 +9,9 @@ the solid, chords and thickness images (kernels: csrc/sdfk_rays.inc).
     hits = render.cast(geometry, origins, directions, t_max=8.0)          # arbitrary rays, (3, N) arrays
     sp = render.spans(geometry, origins, directions, t_max=8.0)           # every crossing, the chord, parity
     xray = render.thickness(geometry, cam, 1920, 1080, t_max=8.0)         # chord per pixel: a radiograph
+    render.illuminate(geometry, img, render.Light.directional((1, 1, 2)), ao_radius=0.2)     # img.shadow, img.ao
+    img.save_pgm("lit.pgm", img.shade(light=(1, 1, 2), shadow=img.shadow, occlusion=img.ao))
+    free = render.visibility(geometry, origins, directions, t_max=3.0)    # is the segment clear of the solid?
 
 No field and no grid are made: the geometry's program (create()'s own) is evaluated along every ray.
 
@@ -86,6 +90,44 @@ split into up to 8 groups by t, and what still does not fit runs every member. T
 minimum at every point of the sphere, so the result has the bits of the kernel without culling (`config.mode =
 MODE_NOCULL` runs that one; tests/test_gpu_render_cull.py compares the two), whatever the order of the rays. Coherent rays
 are what makes it fast: a 1000-sphere union costs a few dozen member evaluations per step instead of 1000.
+
+Secondary rays: what a surface point sees. `visibility` marches arbitrary rays as `cast` does and reports how much of the
+segment [t_min, t_end] is free of the solid (one definition: the kernels, tests/secondary_reference.py and this text), per
+ray i, in float32:
+
+    t = t_min; vis = 1; t_end = min(t_max, limits[i]) if limits is given, else t_max
+    repeat at most max_steps times:
+        f   = field(o + t d)                      # fmaf(t, d, o) per component
+        thr = max(eps, cone * t)
+        if f <= thr: vis = 0; status = HIT; stop  # blocked
+        if k > 0: vis = min(vis, k * (f * (1/L)) / t)     # the penumbra estimate; t = 0 gives +inf, since f > 0
+        t   = t + f / L                           # fmaf(f, float32(1 / L), t); steps += 1
+        if t > t_end: status = MISS; stop         # clear
+    otherwise: status = LIMIT                     # vis is what was seen so far, never folded into 0 or 1
+
+k = `softness`; 0 is the hard test, vis 0 or 1. f / L is the radius of a ball around o + t d that is free of the solid, so
+k (f / L) / t < 1 says the ray passes the solid within the cone of half-angle about 1 / k around it: a light of that angular
+radius is partly hidden, and vis is the smallest such ratio along the ray, the usual soft shadow of distance-field
+tracers (an estimate, never larger than it should be by more than the field's own error: the marched points are points
+of the ray). `t_min` must not be negative, so vis stays in [0, 1]. `limits` is the end of every ray, what a point light
+needs. The advance and both tests are those of `cast`: with `limits=None`, status and steps equal cast's bit for bit.
+
+`ambient_occlusion` measures how open the half-space above a surface point p with unit normal n is, m = `samples` (1 to
+16), in float32:
+
+    occ = 0
+    for i = 1 .. m:
+        h   = radius * float32(i) * float32(1 / m)
+        f   = field(p + h n)                      # fmaf(h, n, p) per component
+        occ = fmaf(2^-i, max(0, h - f * float32(1 / L)), occ)
+    ao = min(1, max(0, 1 - strength * occ * float32(1 / radius)))
+
+Above a plane f / L = h at every sample and ao is exactly 1; whatever else comes within h of a sample lowers f there and
+darkens the point, the near samples counting most. `illuminate` builds both kinds of rays on the host from the hit points
+and the normals of an Image — shadow rays toward a `Light.directional(toward)` or a `Light.point(position)`, from origins
+lifted off the surface by a bias of 4 stencil widths of the pixel — and fills `image.shadow` and `image.ao`;
+`Image.shade(shadow=, occlusion=)` computes ambient * ao + (1 - ambient) * lambert * shadow. Long unions are culled along these rays as along the primary ones, with
+the same bits. Refusals and `lipschitz=` are those of `cast`.
 """
 import contextlib
 import ctypes
@@ -102,6 +144,7 @@ COMPLETE = 0                                  # spans / thickness: the ray was f
 _INSIDE0 = 4                                  # the kernels' status byte carries inside0 as this bit
 MAX_CROSSINGS = 32                            # csrc/sdfk_raydev.h SDFK_SPAN_MAX_CROSSINGS
 SPAN_EPS_FLOOR = 2.0 ** -20                   # eps >= this * max(|t_min|, |t_max|): t + eps > t in float32 on the whole ray
+MAX_AO_SAMPLES = 16                           # csrc/sdfk_raydev.h SDFK_AO_MAX_SAMPLES
 STENCIL_FLOOR = np.float32(2.0 ** -16)        # csrc/sdfk_raydev.h sdfk_ray_stencil_width
 
 
@@ -218,6 +261,56 @@ class RayHits:
         return (o + host(self.t).astype(np.float64)[hit] * d).astype(np.float32)
 
 
+class RayVisibility:
+    """Result of visibility(): vis (N,) float32 in [0, 1] — 0 blocked, 1 clear, between the two in a penumbra —, status (N,)
+    uint8 (MISS 0: clear, the ray passed its end; HIT 1: blocked; LIMIT 2: max_steps reached, vis is what was seen so far),
+    steps (N,) int32 (advances made). With resident=True, vis is a DeviceField; status and steps are host arrays."""
+
+    def __init__(self, vis, status, steps):
+        self.vis, self.status, self.steps = vis, status, steps
+
+    def __repr__(self):
+        return "RayVisibility(%d rays, %d blocked, %d at the step limit)" % (
+            self.status.size, int(np.count_nonzero(self.status == HIT)), int(np.count_nonzero(self.status == LIMIT)))
+
+
+class Light:
+    """A light for illuminate(): Light.directional(toward) — parallel rays, `toward` points from the scene TO the light — or
+    Light.point(position)."""
+
+    def __init__(self, toward=None, position=None):
+        if (toward is None) == (position is None):
+            raise ValueError("a light has a direction (Light.directional) or a position (Light.point)")
+        v = np.asarray(toward if position is None else position, dtype=np.float64).reshape(3)
+        if not np.all(np.isfinite(v)):
+            raise ValueError("the light's vector is not finite")
+        self.position = v if toward is None else None
+        self.toward = None
+        if toward is not None:
+            n = np.linalg.norm(v)
+            if not n > 0.0:
+                raise ValueError("the light direction is the zero vector")
+            self.toward = v / n
+
+    @classmethod
+    def directional(cls, toward):
+        return cls(toward=toward)
+
+    @classmethod
+    def point(cls, position):
+        return cls(position=position)
+
+    def rays(self, points):
+        """-> (unit directions (3, M) float64 from `points` (3, M) toward the light, distances to it (M,) or None for a
+        directional light). A point AT a point light gets the zero direction and the distance 0."""
+        p = np.asarray(points, dtype=np.float64)
+        if self.position is None:
+            return np.repeat(self.toward[:, None], p.shape[1], axis=1), None
+        w = self.position[:, None] - p
+        dist = np.linalg.norm(w, axis=0)
+        return np.divide(w, dist, out=np.zeros_like(w), where=dist > 0), dist
+
+
 class Camera:
     """A pinhole camera (or, from Camera.orthographic, a parallel one); see the module text for the pixel formula."""
 
@@ -298,6 +391,7 @@ class Image:
         self.depth, self.status, self.steps, self.normals = depth, status, steps, normals
         self.t = depth if t is None else t
         self.camera, self.eps, self.cone = camera, eps, cone
+        self.shadow = self.ao = None                            # (H, W) float32 once illuminate() has filled them
 
     def __repr__(self):
         h, w = self.status.shape
@@ -325,10 +419,12 @@ class Image:
         self.normals = out
         return out
 
-    def shade(self, light=(1.0, 1.0, 2.0), ambient=0.15, color=None, background=0.0, dtype=np.uint8):
-        """Lambert shading from normals and status on the host: ambient + (1 - ambient) max(0, n . l) at the hits (l the
-        unit vector TOWARD the light), `background` elsewhere. -> (H, W), or (H, W, 3) with an RGB `color` in [0, 1];
-        uint8 (0..255, rounded) or float32 in [0, 1]."""
+    def shade(self, light=(1.0, 1.0, 2.0), ambient=0.15, color=None, background=0.0, dtype=np.uint8, shadow=None,
+              occlusion=None):
+        """Lambert shading from normals and status on the host: ambient ao + (1 - ambient) max(0, n . l) shadow at the hits
+        (l the unit vector TOWARD the light; `shadow`, `occlusion`: (H, W) arrays in [0, 1] such as illuminate()'s
+        image.shadow and image.ao, None: 1 everywhere), `background` elsewhere. -> (H, W), or (H, W, 3) with an RGB
+        `color` in [0, 1]; uint8 (0..255, rounded) or float32 in [0, 1]."""
         if self.normals is None:
             raise ValueError("shade needs normals: render(..., normals=True) or exact_normals()")
         l = np.asarray(light, dtype=np.float64).reshape(3)
@@ -336,7 +432,15 @@ class Image:
         if not n > 0.0:
             raise ValueError("the light direction is the zero vector")
         lam = np.clip(np.asarray(self.normals, dtype=np.float64).dot(l / n), 0.0, 1.0)
-        value = np.where(self.status == HIT, float(ambient) + (1.0 - float(ambient)) * lam, float(background))
+        lit, amb = (1.0 - float(ambient)) * lam, float(ambient)
+        for name, factor in (("shadow", shadow), ("occlusion", occlusion)):
+            if factor is not None and np.shape(factor) != self.status.shape:
+                raise ValueError("%s must have the image's shape %r; got %r" % (name, self.status.shape, np.shape(factor)))
+        if shadow is not None:
+            lit = lit * np.asarray(shadow, dtype=np.float64)
+        if occlusion is not None:
+            amb = amb * np.asarray(occlusion, dtype=np.float64)
+        value = np.where(self.status == HIT, amb + lit, float(background))
         if color is not None:
             rgb = np.asarray(color, dtype=np.float64).reshape(3)
             value = np.where((self.status == HIT)[..., None], value[..., None] * rgb, float(background))
@@ -367,8 +471,9 @@ class Image:
 
     def save_npz(self, path):
         arrays = {"depth": self.depth, "status": self.status, "steps": self.steps, "t": self.t}
-        if self.normals is not None:
-            arrays["normals"] = self.normals
+        for name in ("normals", "shadow", "ao"):
+            if getattr(self, name) is not None:
+                arrays[name] = getattr(self, name)
         np.savez_compressed(path, **arrays)
 
 
@@ -652,3 +757,156 @@ def thickness(geometry, camera, width, height, t_min=0.0, t_max=100.0, max_steps
         crossings = cross.download_rows().reshape(k, height, width) if k else None
     return ThicknessImage(chord, count.reshape(height, width), status.reshape(height, width), steps.reshape(height, width),
                           crossings, camera=camera, eps=float(eps), cone=float(cone), t_min=t_min, t_max=t_max)
+
+
+def visibility(geometry, origins, directions, t_min=0.0, t_max=100.0, eps=1e-4, cone=0.0, max_steps=256, lipschitz=None,
+               softness=0.0, limits=None, resident=False):
+    """How much of each ray's segment [t_min, min(t_max, limits)] is free of `geometry`: 0 blocked, 1 clear, and with
+    `softness` = k > 0 the penumbra estimate min k (f / L) / t in between. `origins`, `directions` as for cast(); `limits`:
+    (N,) per-ray ends (host array or DeviceField) or None. -> RayVisibility. See the module text for the rule."""
+    options = _options(t_min, t_max, eps, cone, max_steps)
+    if options[0] < 0.0:
+        raise ValueError("t_min must not be negative (vis stays in [0, 1] without a clamp); got %g" % options[0])
+    softness = float(softness)
+    if not (np.isfinite(softness) and softness >= 0.0):
+        raise ValueError("softness must be finite and not negative; got %r" % (softness,))
+    low, inv = _lowered(geometry, lipschitz)
+    n = _check_rays(origins, directions)                        # (before anything asks for the GPU)
+    if limits is not None:
+        n_l = limits.n if isinstance(limits, _engine.DeviceField) else np.shape(limits)
+        if n_l != (n if isinstance(limits, _engine.DeviceField) else (n,)):
+            raise ValueError("limits must have shape (%d,), one end per ray; got %r" % (n, n_l))
+    prog = _on_device(low)
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        source = stack.enter_context(_source(rays=(origins, directions, n)))
+        vis = on_error.enter_context(_engine.DeviceField(n, config.device))
+        d_status = stack.enter_context(_engine.DeviceBuffer(max(n, 64), what="render"))
+        d_steps = stack.enter_context(_engine.DeviceBuffer(max(n, 16) * 4, what="render"))
+        d_limits = None
+        if limits is not None and n:
+            lim = limits if isinstance(limits, _engine.DeviceField) else \
+                stack.enter_context(_engine.DeviceField.from_host(limits, config.device))
+            d_limits = lim.at()
+        status, steps = _march("sdfk_visibility_rays_device", prog, source, options, inv,
+                               (softness, d_limits, vis.at(), d_status.at(), d_steps.at()), n, d_status, d_steps)
+        if resident:
+            on_error.pop_all()
+            return RayVisibility(vis, status, steps)
+        return RayVisibility(vis.numpy(), status, steps)
+
+
+def ambient_occlusion(geometry, points, normals, radius, samples=5, strength=1.0, lipschitz=None, resident=False):
+    """Ambient occlusion of the surface points `points` with the unit `normals` (both as the rays of cast()): 1 open, 0
+    closed; `samples` (1 to 16) field evaluations per point along the normal, out to `radius`. -> (N,) float32, or a
+    DeviceField with resident=True. See the module text for the rule."""
+    radius, strength, samples = float(radius), float(strength), int(samples)
+    if not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError("radius must be finite and positive; got %r" % (radius,))
+    if not 1 <= samples <= MAX_AO_SAMPLES:
+        raise ValueError("samples from 1 to %d; got %r" % (MAX_AO_SAMPLES, samples))
+    if not (np.isfinite(strength) and strength >= 0.0):
+        raise ValueError("strength must be finite and not negative; got %r" % (strength,))
+    low, inv = _lowered(geometry, lipschitz)
+    n = _check_rays(points, normals)                            # (before anything asks for the GPU)
+    prog = _on_device(low)
+    with contextlib.ExitStack() as on_error, contextlib.ExitStack() as stack:
+        source = stack.enter_context(_source(rays=(points, normals, n)))
+        ao = on_error.enter_context(_engine.DeviceField(n, config.device))
+        L = _engine.lib()
+        _engine.check(L.sdfk_occlusion_rays_device(prog.handle, *source, radius, samples, strength, inv, ao.at(), None,
+                                                   config.mode), "sdfk_occlusion_rays_device")
+        _engine.check(L.sdfk_sync(None), "sdfk_sync")
+        if resident:
+            on_error.pop_all()
+            return ao
+        return ao.numpy()
+
+
+BIAS_WIDTHS = 4.0             # illuminate(): the default bias in stencil widths of the pixel
+
+
+def shadow_rays(image, light, bias=None):
+    """The secondary rays illuminate() marches for the shadow of `light` -> (facing, origins, directions, limits, eps):
+    `facing` (M,) bool marks, among the M hit pixels in row-major order, those that face the light (n . l > 0, and a unit
+    normal: a degenerate stencil leaves the zero vector); they have a ray each: `origins`, `directions` (3, F) float32,
+    `limits` (F,) float32 — the distance from the origin to a point light — or None, and `eps`, the threshold of the march:
+    half the smallest bias. See illuminate() for the rule."""
+    if not isinstance(light, Light):
+        raise TypeError("light must be a render.Light; got %r" % (type(light).__name__,))
+    if image.normals is None or image.camera is None:
+        raise ValueError("secondary rays need an Image with normals and its camera: render(..., normals=True)")
+    hit = image.status == HIT
+    nrm = np.asarray(image.normals, dtype=np.float64)[hit].T    # (3, M), row-major pixel order
+    p32 = image.points()
+    if bias is None:
+        lift = BIAS_WIDTHS * stencil_width(image.t[hit], p32, image.eps, image.cone).astype(np.float64)
+    else:
+        if not (np.isfinite(float(bias)) and float(bias) > 0.0):
+            raise ValueError("bias must be finite and positive; got %r" % (bias,))
+        lift = np.full(p32.shape[1], float(bias))
+    org = p32.astype(np.float64) + lift * nrm
+    to_light, dist = light.rays(org)
+    facing = ((nrm * to_light).sum(axis=0) > 0.0) & (np.abs((nrm * nrm).sum(axis=0) - 1.0) <= 1e-5)
+    d32 = to_light[:, facing].astype(np.float32).astype(np.float64)
+    d32 = np.divide(d32, np.linalg.norm(d32, axis=0)).astype(np.float32)
+    limits = None if dist is None else dist[facing].astype(np.float32)
+    return facing, org[:, facing].astype(np.float32), d32, limits, 0.5 * float(lift[facing].min()) if facing.any() else 0.0
+
+
+def tile_order(mask):
+    """The True pixels of the (H, W) `mask`, numbered in row-major order -> those numbers sorted by 8 x 8 pixel tile (tiles
+    in row-major order, the pixels of a tile in row-major order): 64 consecutive entries lie close together in the image, as
+    the 64 rays of a wave of the camera kernels do. The culled kernels bound a wave's points by one sphere, and a run of 64
+    pixels along an image row makes a far larger one (DESIGN 4.19 has the measurement); results do not depend on the order."""
+    iy, ix = np.nonzero(mask)
+    key = ((iy >> 3) * ((mask.shape[1] + 7) // 8) + (ix >> 3)) * 64 + (iy & 7) * 8 + (ix & 7)
+    return np.argsort(key, kind="stable")
+
+
+def _pixel_order(hit, among):
+    """tile_order of the hit pixels marked by `among` (M,) bool."""
+    mask = np.zeros(hit.shape, dtype=bool)
+    mask[hit] = among
+    return tile_order(mask)
+
+
+def illuminate(geometry, image, light, softness=8.0, bias=None, ao_radius=None, ao_samples=5, ao_strength=1.0, lipschitz=None,
+               max_steps=256, t_max=None):
+    """Shadows and ambient occlusion of a rendered Image (render(..., normals=True), or exact_normals()): fills
+    `image.shadow` — visibility of the `light` from every hit pixel, (H, W) float32 — and, when `ao_radius` is given,
+    `image.ao` (ambient_occlusion with `ao_samples`, `ao_strength` at the hit points); both are 1 where the pixel did not
+    hit. -> the image.
+
+    The secondary rays are built on the host (shadow_rays; marched in the order of tile_order), in float64 from Image.points() and the normals, and rounded to
+    float32: origin p + bias n, direction toward the light (renormalised after rounding), for a point light `limits` = the
+    distance from the origin to the light. Pixels with n . l <= 0 face away and get shadow 0 without a ray. `bias` lifts the
+    origin off the surface it lies on: by default BIAS_WIDTHS = 4 times the pixel's own stencil width (stencil_width: its
+    hit threshold max(eps, cone t), floored at 2^-16 max|p|) — the hit point lies within one threshold of the surface, so
+    the origin is at least three thresholds clear of it and a convex body never shadows itself —, or the given length for
+    all pixels. The shadow march runs with cone = 0 and eps = half the smallest bias, so no ray starts within its own hit
+    threshold, and as far as `t_max` (default: the image's longest ray, image.t.max(), for a directional light; the
+    largest distance to a point light). `softness`, `max_steps`, `lipschitz` as in visibility()."""
+    facing, origins, directions, limits, eps = shadow_rays(image, light, bias)
+    hit = image.status == HIT
+    shadow = np.zeros(facing.size, dtype=np.float32)
+    if facing.any():
+        if t_max is None:
+            t_max = float(np.max(image.t)) if limits is None else float(limits.max())
+        order = _pixel_order(hit, facing)                       # (rays of one wave from one tile of the image)
+        vis = np.empty(order.size, dtype=np.float32)
+        vis[order] = visibility(geometry, np.ascontiguousarray(origins[:, order]), np.ascontiguousarray(directions[:, order]), 0.0,
+                                t_max, eps, 0.0, max_steps, lipschitz, softness, None if limits is None else limits[order]).vis
+        shadow[facing] = vis
+    image.shadow = np.ones(hit.shape, dtype=np.float32)
+    image.shadow[hit] = shadow
+    if ao_radius is not None:
+        nrm = np.ascontiguousarray(np.asarray(image.normals, dtype=np.float32)[hit].T)
+        unit = np.abs((nrm.astype(np.float64) ** 2).sum(axis=0) - 1.0) <= 1e-5      # (no AO on a degenerate stencil)
+        ao = np.ones(facing.size, dtype=np.float32)
+        if unit.any():
+            order = np.flatnonzero(unit)[_pixel_order(hit, unit)]
+            ao[order] = ambient_occlusion(geometry, np.ascontiguousarray(image.points()[:, order]),
+                                          np.ascontiguousarray(nrm[:, order]), ao_radius, ao_samples, ao_strength, lipschitz)
+        image.ao = np.ones(hit.shape, dtype=np.float32)
+        image.ao[hit] = ao
+    return image

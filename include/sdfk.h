@@ -112,6 +112,10 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
                                       (sdfk_span_rays_device / sdfk_span_camera_device) around the same body; long chains get
                                       the culled pair as RAYS does. As RAYS: no cull sites needed, no FLAGS / XY build, not
                                       part of sdfk_program_compile_check. */
+#define SDFK_FLAVOUR_SECONDARY 13  /* sdfk_spec_visibility / sdfk_spec_occlusion: the secondary marches (sdfk_visibility_rays_device /
+                                      sdfk_occlusion_rays_device) around the same body, array rays only; long chains get a
+                                      culled pair as RAYS does. As RAYS: no cull sites needed, no FLAGS / XY build, not part of
+                                      sdfk_program_compile_check. */
 /* OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (one bit per point, value <= threshold, instead of
    the field — what sdfk_eval_device_select / sdfk_eval_grid_select launch). A translation unit of its own: the field
    kernels carry none of it (as a run-time branch it cost the 20-primitive tree 10 % at 1025^3). */
@@ -607,6 +611,40 @@ int sdfk_span_camera_device(sdfk_program* prog, const float* camera, int width, 
                             float t_max, float eps, float cone, float inv_lipschitz, int max_steps, float* d_chord,
                             int* d_count, unsigned char* d_status, int* d_steps, float* d_crossings, int64_t crossing_stride,
                             int max_crossings, void* stream, int mode);
+
+/* ---- secondary rays: what a surface point sees (csrc/sdfk_raydev.h: sdfk_trace_visibility, sdfk_trace_occlusion) ------
+ * Visibility: how much of the segment [t_min, t_end] of a ray is free of the solid. Per ray i, in fp32:
+ *     t = t_min; vis = 1; t_end = d_limits ? min(t_max, d_limits[i]) : t_max
+ *     repeat at most max_steps times:
+ *         f = field(o + t d);  thr = max(eps, cone * t)
+ *         if f <= thr: vis = 0; status 1 (blocked), stop
+ *         if softness > 0: vis = min(vis, softness * (f * inv_lipschitz) / t)       (t = 0: +inf, since f > 0)
+ *         t = fmaf(f, inv_lipschitz, t);  steps += 1
+ *         if t > t_end: status 0 (clear), stop
+ *     otherwise: status 2 (step limit; vis is what was seen so far)
+ * The advance and the two tests are those of sdfk_trace_rays_device: with d_limits NULL, d_status and d_steps are the
+ * bytes that call writes, whatever the softness. softness = 0 is the hard test (vis is 0 or 1); with softness = k a ray
+ * that passes the solid at a distance below t / k sees less than 1 (a light of angular radius about 1 / k). t_min >= 0,
+ * so that vis lies in [0, 1]. d_limits (nullable): n floats, the end of every ray — the distance to a point light.
+ * Outputs, one entry per ray: d_vis (fp32), d_status (1 byte), d_steps (int32). Asynchronous on `stream`; `mode` as for
+ * sdfk_trace_rays_device (SDFK_FLAVOUR_SECONDARY; interpreter and specialised kernels give the same bits; long chains
+ * are culled per wave except under SDFK_MODE_NOCULL, same bits). Validated on the host, -1 and no launch: what
+ * sdfk_trace_rays_device refuses, t_min < 0, a negative or non-finite softness, a NULL d_vis / d_status / d_steps. */
+int sdfk_visibility_rays_device(sdfk_program* prog, const float* d_origins, int64_t origin_stride, const float* d_directions,
+                                int64_t direction_stride, int64_t n, float t_min, float t_max, float eps, float cone,
+                                float inv_lipschitz, int max_steps, float softness, const float* d_limits, float* d_vis,
+                                unsigned char* d_status, int* d_steps, void* stream, int mode);
+/* Ambient occlusion of n points with unit normals (two (3, n) device arrays, rows strided as above). Per point, in fp32:
+ *     occ = 0
+ *     for i = 1 .. samples:  h = radius * i * (1 / samples);  f = field(p + h n)
+ *                            occ = fmaf(2^-i, max(0, h - f * inv_lipschitz), occ)
+ *     ao = min(1, max(0, 1 - strength * occ * (1 / radius)))           (1 / samples, 1 / radius rounded to fp32 once)
+ * 1 above a plane, smaller where the solid comes closer to the samples than the point's own surface. d_ao: n floats.
+ * `stream` and `mode` as above. -1 and no launch: radius not finite or <= 0, samples outside 1 ... 16, strength negative
+ * or not finite, a bad inv_lipschitz, a NULL d_ao, n < 0, a row stride below n. */
+int sdfk_occlusion_rays_device(sdfk_program* prog, const float* d_points, int64_t point_stride, const float* d_normals,
+                               int64_t normal_stride, int64_t n, float radius, int samples, float strength,
+                               float inv_lipschitz, float* d_ao, void* stream, int mode);
 
 /* ---- sub-voxel occupancy (aegolius_amd.occupancy; csrc/sdfk_occupancy.inc, csrc/sdfk_occdev.h) ---------------------
  * Per cell of the grid of the axis tables (flat index (i0 n1 + i1) n2 + i2), the fraction of its K = k0 k1 k2 sub-sample
