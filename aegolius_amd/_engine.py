@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "libsdfk.so")
 MODE_AUTO, MODE_INTERPRET, MODE_SPECIALIZED, MODE_NOCULL = 0, 1, 2, 3
 (FLAVOUR_PLAIN_ARRAY, FLAVOUR_PLAIN_GRID, FLAVOUR_TILE_ARRAY, FLAVOUR_TILE_GRID, FLAVOUR_TILE_MASK, FLAVOUR_ROWS_ARRAY,
  FLAVOUR_ROWS_GRID, FLAVOUR_ROWS_MASK, FLAVOUR_ROWS2D_ARRAY, FLAVOUR_ROWS2D_GRID, FLAVOUR_RAYS, FLAVOUR_OCCUPANCY,
- FLAVOUR_SPANS, FLAVOUR_SECONDARY) = range(14)
+ FLAVOUR_SPANS, FLAVOUR_SECONDARY, FLAVOUR_MOMENTS) = range(15)
 FLAVOUR_FLAGS = 0x100      # OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (fused selection)
 FLAVOUR_XY = 0x200         # OR-ed onto PLAIN_ARRAY / ROWS2D_ARRAY: the build for two-row coordinates (z = 0 by contract)
 
@@ -150,6 +150,9 @@ SIGNATURES = {
     "sdfk_eval_grid_occupancy": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float,
                                         _c.c_float, _vp, _vp, _i64, _c.POINTER(_i64), _c.POINTER(_i64), _fp, _vp, _int]),
     "sdfk_field_row_sums": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "sdfk_eval_grid_moments_scratch": (_sz, [_i64, _i64, _i64, _i64]),
+    "sdfk_eval_grid_moments": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _c.c_float,
+                                      _c.c_float, _vp, _sz, _i64, _c.POINTER(_c.c_uint64), _c.POINTER(_i64), _fp, _vp, _int]),
     "sdfk_field_redistance_scratch": (_sz, [_i64, _i64, _i64]),
     "sdfk_field_redistance": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _int, _vp, _vp,
                                      _c.POINTER(_i64), _fp, _vp]),
@@ -566,6 +569,40 @@ class Program:
             for name, value in zip(("centre", "classify", "sample"), ms):
                 timings[name] = timings.get(name, 0.0) + float(value)
         return int(inside.value), int(near.value)
+
+    def moments_grid(self, axes, sub_tables, half_widths, samples, level, lipschitz, slab_cells=0, device=0, mode=MODE_AUTO,
+                     timings=None):
+        """Integer moments of the solid on the sub-sample lattice of occupancy_grid (sdfk_eval_grid_moments; tables and
+        `lipschitz` as there): the sums of 1, u_a and u_a u_b over the inside sub-samples, u_a = 2 (i_a k_a + j_a) + 1.
+        aegolius_amd.moments builds the tables, states the definition and turns the sums into physical quantities.
+        -> ((N, U0, U1, U2, U00, U01, U02, U11, U12, U22), near cells) as Python ints. `timings`: a dict that receives
+        device-event milliseconds of centre / far / sample."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(axes)
+        if len(ax) != 3 or len(sub_tables) != 3 or len(half_widths) != 3:
+            raise ValueError("moments_grid: three axis, sub-sample and half-width tables")
+        k = [int(samples) if a.size > 1 else 1 for a in ax]
+        sub = [np.ascontiguousarray(t, dtype=np.float32) for t in sub_tables]
+        hw = [np.ascontiguousarray(t, dtype=np.float32) for t in half_widths]
+        for a, s, h, ka in zip(ax, sub, hw, k):
+            if s.shape != (a.size * ka,) or h.shape != (a.size,):
+                raise ValueError("moments_grid: an axis of %d points takes %d sub-samples and %d half-widths; got %r and %r"
+                                 % (a.size, a.size * ka, a.size, s.shape, h.shape))
+        shape = [a.size for a in ax]
+        words, near = (_c.c_uint64 * 20)(), _i64(0)
+        ms = (_c.c_float * 3)() if timings is not None else None
+        nbytes = L.sdfk_eval_grid_moments_scratch(*shape, int(slab_cells))
+        with DeviceBuffer(nbytes, what="moments") as scratch:
+            check(L.sdfk_eval_grid_moments(self._h, *tab, *[_ptr(s) for s in sub], *[_ptr(h) for h in hw], int(samples),
+                                           float(level), float(lipschitz), scratch.at(), nbytes, int(slab_cells), words,
+                                           ctypes.byref(near), ms, None, mode),
+                  "sdfk_eval_grid_moments")
+        if timings is not None:
+            for name, value in zip(("centre", "far", "sample"), ms):
+                timings[name] = timings.get(name, 0.0) + float(value)
+        return tuple(int(words[2 * t]) + (int(words[2 * t + 1]) << 64) for t in range(10)), int(near.value)
 
     def select_host(self, co, threshold=0.0, device=0, mode=MODE_AUTO):
         """The same for a (3, N) host array (uploaded once as float32; the row-length hint is detected like create())."""

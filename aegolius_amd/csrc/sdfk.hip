@@ -1227,5 +1227,6 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_mesh.inc"
 #include "sdfk_rays.inc"
 #include "sdfk_occupancy.inc"
+#include "sdfk_moments.inc"
 #include "sdfk_redistance.inc"
 #include "sdfk_enclosure.inc"

@@ -145,6 +145,23 @@ extern "C" __global__ __launch_bounds__(SDFK_OCC_BLOCK) void sdfk_spec_occ_all(
 }
 )SDFKW";
 
+// Mass properties (SDFK_FL_MOMENTS): the sample pass of sdfk_momdev.h around the same field object, over a list of cells
+// or over all cells of a slab; the same text as the interpreter kernel (sdfk_moments.inc) but for the evaluator.
+static const char kMoments[] = R"SDFKW(
+extern "C" __global__ __launch_bounds__(SDFK_OCC_BLOCK) void sdfk_spec_mom_list(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkOccList src, sdfk_occgrid grid, unsigned waves,
+    unsigned long long* __restrict__ partial) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_mom_sample(src, field, grid, waves, partial);
+}
+extern "C" __global__ __launch_bounds__(SDFK_OCC_BLOCK) void sdfk_spec_mom_all(
+    const float* __restrict__ PRM, const float* __restrict__ TAB, SdfkOccAll src, sdfk_occgrid grid, unsigned waves,
+    unsigned long long* __restrict__ partial) {
+    const SdfkSpecField field = {PRM, TAB};
+    sdfk_mom_sample(src, field, grid, waves, partial);
+}
+)SDFKW";
+
 // Pieces shared by the two culling kernel families.
 static const char kWaveHelpers[] = R"SDFKH(
 #ifndef SDFK_TWAVES
@@ -2543,7 +2560,8 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
     g.s += "\n";
     g.s += kEmbeddedAccess;
     char buf[64];
-    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY || flavour == SDFK_FL_SPANS || flavour == SDFK_FL_SECONDARY) {
+    if (flavour == SDFK_FL_RAYS || flavour == SDFK_FL_OCCUPANCY || flavour == SDFK_FL_SPANS || flavour == SDFK_FL_SECONDARY ||
+        flavour == SDFK_FL_MOMENTS) {
         // Sphere tracing: the plain body, one ray per lane (scalar T: lanes diverge per ray, and two rays per lane would
         // double every wave's tail), inside the marching loop of sdfk_raydev.h. A long hard union that the field kernels
         // run table-driven ("chain mode") keeps its table-driven plain body, which builds in a second whatever the number
@@ -2570,6 +2588,15 @@ std::string sdfk_generate_source(const sdfk_opinfo* ops, int n_ops, const uint32
             g.s += kEmbeddedOccdev;
             g.s += kSpecField;
             g.s += kOccupancy;
+            return g.s;
+        }
+        if (flavour == SDFK_FL_MOMENTS) {
+            // the sample pass of the mass properties: the occupancy flavour's body and field object inside sdfk_mom_sample
+            // (sdfk_occdev.h comes first for the grid description and the entry sources)
+            g.s += kEmbeddedOccdev;
+            g.s += kEmbeddedMomdev;
+            g.s += kSpecField;
+            g.s += kMoments;
             return g.s;
         }
         g.s += kEmbeddedRaydev;

@@ -45,6 +45,7 @@ enum sdfk_flavour {
     SDFK_FL_OCCUPANCY,         // sdfk_spec_occ_list + sdfk_spec_occ_all: the sample pass of sdfk_occdev.h around sdfk_point<float>
     SDFK_FL_SPANS,             // sdfk_spec_spans + sdfk_spec_spancam: every crossing and the chord (sdfk_trace_spans, sdfk_raydev.h)
     SDFK_FL_SECONDARY,         // sdfk_spec_visibility + sdfk_spec_occlusion: the secondary marches (sdfk_trace_visibility, sdfk_trace_occlusion)
+    SDFK_FL_MOMENTS,           // sdfk_spec_mom_list + sdfk_spec_mom_all: the sample pass of sdfk_momdev.h around sdfk_point<float>
     SDFK_FL_COUNT,
     SDFK_FL_ALL = SDFK_FL_COUNT   // every evaluation flavour in one unit (sdfk_program_source, developer tools)
 };

@@ -405,7 +405,7 @@ static const char* const kFlavourFn[SDFK_FL_COUNT][2] = {
     {"sdfk_spec_tmask", nullptr},     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr}, {"sdfk_spec_rmask", nullptr},
     {"sdfk_spec_r", nullptr},         {"sdfk_spec_rg", nullptr},        {"sdfk_spec_rays", "sdfk_spec_raycam"},
     {"sdfk_spec_occ_list", "sdfk_spec_occ_all"},                        {"sdfk_spec_spans", "sdfk_spec_spancam"},
-    {"sdfk_spec_visibility", "sdfk_spec_occlusion"}};
+    {"sdfk_spec_visibility", "sdfk_spec_occlusion"},                    {"sdfk_spec_mom_list", "sdfk_spec_mom_all"}};
 // the march flavours: built by the first call that needs them, from programs with or without cull sites, one build each
 static bool march_flavour(int f) { return f == SDFK_FL_RAYS || f == SDFK_FL_SPANS || f == SDFK_FL_SECONDARY; }
 // ... and the second pair of kernels that long chains get in them (culling along the rays, sdfk_raycull.h): fn[2], fn[3]
@@ -558,6 +558,7 @@ extern "C" int sdfk_program_compile_check(sdfk_program* p, size_t* code_size) {
     for (int f = 0; f < SDFK_FL_COUNT; ++f) {
         if (march_flavour(f)) continue;                         // (not evaluation flavours: built by the first cast / span / secondary call)
         if (f == SDFK_FL_OCCUPANCY) continue;                   // (nor this one: built by the first occupancy call)
+        if (f == SDFK_FL_MOMENTS) continue;                     // (nor this one: built by the first moments call)
         if (p->sites.empty() && f != SDFK_FL_PLAIN_ARRAY && f != SDFK_FL_PLAIN_GRID) continue;
         if (p->chain_mode && (f == SDFK_FL_TILE_ARRAY || f == SDFK_FL_TILE_GRID || f == SDFK_FL_TILE_MASK || f == SDFK_FL_ROWS_MASK)) continue;
         std::shared_ptr<CodeObject> e = code_get(flavour_key(p, f, rwb), [&] { return flavour_source(p, f); }, rwb, true);
@@ -576,12 +577,14 @@ extern "C" int sdfk_program_compile_flavour(sdfk_program* p, int flavour, size_t
     if (flavour >= 0) flavour &= ~(SDFK_FLAVOUR_FLAGS | SDFK_FLAVOUR_XY);
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_program_compile_flavour: unknown flavour");
     if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && !march_flavour(flavour) &&
-        flavour != SDFK_FL_OCCUPANCY)
+        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_MOMENTS)
         return fail(-2, "sdfk_program_compile_flavour: the program has no cull sites");
     if (with_flags && flavour == SDFK_FL_RAYS)
         return fail(-2, "sdfk_program_compile_flavour: the ray flavour has no flag-writing or two-row build");
     if (with_flags && flavour == SDFK_FL_OCCUPANCY)
         return fail(-2, "sdfk_program_compile_flavour: the occupancy flavour has no flag-writing or two-row build");
+    if (with_flags && flavour == SDFK_FL_MOMENTS)
+        return fail(-2, "sdfk_program_compile_flavour: the moments flavour has no flag-writing or two-row build");
     if (with_flags && flavour == SDFK_FL_SPANS)
         return fail(-2, "sdfk_program_compile_flavour: the span flavour has no flag-writing or two-row build");
     if (with_flags && flavour == SDFK_FL_SECONDARY)
@@ -606,7 +609,7 @@ extern "C" int sdfk_debug_compile_external(sdfk_program* p, int flavour, size_t*
     if (!p) return fail(-1, "null program");
     if (flavour < 0 || flavour >= SDFK_FL_COUNT) return fail(-1, "sdfk_debug_compile_external: unknown flavour");
     if (p->sites.empty() && flavour != SDFK_FL_PLAIN_ARRAY && flavour != SDFK_FL_PLAIN_GRID && !march_flavour(flavour) &&
-        flavour != SDFK_FL_OCCUPANCY)
+        flavour != SDFK_FL_OCCUPANCY && flavour != SDFK_FL_MOMENTS)
         return fail(-2, "sdfk_debug_compile_external: the program has no cull sites");
     if (!rtc_helper_available()) return fail(-9, "sdfk_rtc_helper is not next to libsdfk.so (or hiprtc cannot be located)");
     std::vector<char> co;

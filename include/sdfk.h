@@ -116,6 +116,9 @@ int sdfk_program_compile_check(sdfk_program* prog, size_t* code_size);
                                       sdfk_occlusion_rays_device) around the same body, array rays only; long chains get a
                                       culled pair as RAYS does. As RAYS: no cull sites needed, no FLAGS / XY build, not part of
                                       sdfk_program_compile_check. */
+#define SDFK_FLAVOUR_MOMENTS 14    /* sdfk_spec_mom_list / sdfk_spec_mom_all: the sample pass of sdfk_eval_grid_moments around the
+                                      same body, one sub-sample per lane (csrc/sdfk_momdev.h); as OCCUPANCY: no cull sites
+                                      needed, no FLAGS / XY build, not part of sdfk_program_compile_check. */
 /* OR-ed onto a PLAIN / ROWS / ROWS2D flavour: its flag-writing build (one bit per point, value <= threshold, instead of
    the field — what sdfk_eval_device_select / sdfk_eval_grid_select launch). A translation unit of its own: the field
    kernels carry none of it (as a run-time branch it cost the 20-primitive tree 10 % at 1025^3). */
@@ -673,6 +676,28 @@ int sdfk_eval_grid_occupancy(sdfk_program* prog, const float* ax0, int64_t n0, c
 /* d_out[r] = sum over i of d_field[r row_len + i] * weights[i] in float64, in a fixed order (weights: HOST, row_len
  * doubles; d_out: rows doubles, DEVICE). What the volume of the fractions is reduced with. Synchronous. */
 int sdfk_field_row_sums(const float* d_field, int64_t rows, int64_t row_len, const double* weights, double* d_out, void* stream);
+
+/* ---- mass properties (aegolius_amd.moments; csrc/sdfk_moments.inc, csrc/sdfk_momdev.h) -------------------------------
+ * The integer moments of the solid on the sub-sample lattice of sdfk_eval_grid_occupancy — same tables, same "inside",
+ * same far rule, same slabs, every argument up to `lipschitz` as there. Sub-sample j_a of grid point i_a has the odd
+ * lattice coordinate u_a = 2 (i_a k_a + j_a) + 1; over all inside sub-samples,
+ *     M = (N, U0, U1, U2, U00, U01, U02, U11, U12, U22) = the sums of 1, u_a, u_a u_b   (an axis of one point: u = 1).
+ * moments_out: HOST, 20 uint64 — M[t] = moments_out[2 t] + 2^64 moments_out[2 t + 1], exact, whatever the order of the
+ * waves: the device keeps 64-bit partial sums per wave, the host adds them in 128 bits. Far cells on the inside enter
+ * in closed form (no field evaluation), near cells are sampled, one sub-sample per lane; *near_cells = the cells that
+ * were sampled, the number sdfk_eval_grid_occupancy reports. No per-cell output is made. d_scratch: scratch_bytes >=
+ * *_scratch bytes (8 per slab cell, 8 per 1024 slab cells and the partials: at most 11 MB), 256-byte aligned. pass_ms
+ * (nullable): 3 floats that receive device-event milliseconds of the centre values, the far pass (classification and
+ * the far cells' sums) and the sampling. `mode` as for sdfk_eval_grid_occupancy (SDFK_FLAVOUR_MOMENTS). -1 and no
+ * launch: a NULL pointer, samples, a NaN level, a bad bound, an unknown mode, too small a scratch buffer, an axis of 2^31
+ * sub-samples or more; -2 and no launch: a grid so long that a 64-bit partial could wrap. Programs with auxiliary fields
+ * are refused (sdfk_program_rays_check). Synchronous: the stream is idle on return. */
+size_t sdfk_eval_grid_moments_scratch(int64_t n0, int64_t n1, int64_t n2, int64_t slab_cells);
+int sdfk_eval_grid_moments(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                           int64_t n2, const float* sub0, const float* sub1, const float* sub2, const float* hw0,
+                           const float* hw1, const float* hw2, int samples, float level, float lipschitz, void* d_scratch,
+                           size_t scratch_bytes, int64_t slab_cells, uint64_t* moments_out, int64_t* near_cells,
+                           float* pass_ms, void* stream, int mode);
 
 /* ---- redistancing (aegolius_amd.redistance; csrc/sdfk_redistance.inc) ------------------------------------------------
  * d_out[p] = the signed Euclidean distance of grid point p (flat index (i0 n1 + i1) n2 + i2) to the level set of the
