@@ -15,5 +15,6 @@ from . import mesh  # noqa: F401
 from . import render  # noqa: F401
 from . import redistance  # noqa: F401
 from . import enclosure  # noqa: F401
+from . import surface  # noqa: F401
 
 __version__ = "0.1.0"

@@ -107,6 +107,11 @@ SIGNATURES = {
     "sdfk_dual_has_rule": (_int, [_int]),
     "sdfk_program_jvp_check": (_int, [_vp, _c.POINTER(_int)]),
     "sdfk_eval_jvp_device": (_int, [_vp, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _i64, _vp]),
+    "sdfk_project_points_device": (_int, [_vp, _vp, _i64, _i64, _c.c_float, _c.c_float, _int, _c.c_float, _vp, _i64, _vp, _vp,
+                                          _i64, _vp, _vp, _vp]),
+    "sdfk_project_workgroups": (_i64, [_i64]),
+    "sdfk_project_points_counted_device": (_int, [_vp, _vp, _i64, _i64, _c.c_float, _c.c_float, _int, _c.c_float, _vp, _i64,
+                                                  _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sdfk_value_jvp_device": (_int, [_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_program_vjp_check": (_int, [_vp, _c.POINTER(_int), _c.POINTER(_i64)]),
     "sdfk_vjp_limits": (_int, [_c.POINTER(_int), _c.POINTER(_int)]),

@@ -201,6 +201,7 @@ struct DevState {
     uint2* d_code = nullptr;
     float* d_params = nullptr;
     float* d_tables = nullptr;
+    float* d_ptan0 = nullptr;  // 3 rows of zero parameter tangents (sdfk_project.inc), made on first use
     unsigned long long params_version = 0;
     std::map<hipStream_t, CellScratch> cells;
 };
@@ -447,6 +448,7 @@ static void free_dev_state(sdfk_program* p) {
         if (kv.second.d_code) (void)hipFree(kv.second.d_code);
         if (kv.second.d_params) (void)hipFree(kv.second.d_params);
         if (kv.second.d_tables) (void)hipFree(kv.second.d_tables);
+        if (kv.second.d_ptan0) (void)hipFree(kv.second.d_ptan0);
         for (auto& cs : kv.second.cells)
             if (cs.second.buf) (void)hipFree(cs.second.buf);
     }
@@ -1222,6 +1224,7 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_hosttree.inc"
 #include "sdfk_lcwg.inc"
 #include "sdfk_dual.inc"
+#include "sdfk_project.inc"
 #include "sdfk_adjoint.inc"
 #include "sdfk_points.inc"
 #include "sdfk_mesh.inc"

@@ -581,6 +581,20 @@ SDFK_DUAL_V_C(dual_prim_cone) {
     }
     SDFK_KLOOP dd[k] = ta ? dA[k] : dB[k];
     SDFK_KLOOP r.d[k] = sg * dd[k] * half_inv;
+    // Free foot on the side, and the side decides the sign: the value is -cr / |q|, cr = w x q, smooth through the surface.
+    // Its tangent is taken from that form: the residual (ax, ay) above is a difference of nearly equal numbers within
+    // 1e-7 |w| of the surface, where its direction is rounding noise and its length 0 exactly on it — and a projection
+    // onto the surface (sdfk_project.inc) ends there. Both forms are equal in exact arithmetic, parameter terms included.
+    const float cr = sd_fma(w0, q1, -w1 * q0);
+    if (ta && u1 > 0.0f && u1 < 1.0f && -cr >= -(w1 - q1)) {
+        const float rs = sd_sqrt(P[3]), half_inv_rs = 0.5f * sdd_rcp(rs);
+        SDFK_KLOOP {
+            const float dcr = dw0[k] * q1 + w0 * SDFK_DQ(k, 1) - dw1[k] * q0 - w1 * SDFK_DQ(k, 0);
+            r.d[k] = -(dcr * rs + cr * (SDFK_DQ(k, 3) * half_inv_rs));
+        }
+    }
+    // Free foot on the base, and the base decides the sign: bx is 0 but for its rounding, the value is -(w1 - q1).
+    if (!ta && u2 > 0.0f && u2 < 1.0f && -(w1 - q1) >= -cr) SDFK_KLOOP r.d[k] = -(dw1[k] - SDFK_DQ(k, 1));
     return r;
 }
 SDFK_DUAL_V_C(dual_prim_zslab) {

@@ -50,6 +50,14 @@ class Mesh:
         self.normals = np.ascontiguousarray(np.divide(g, norm, out=np.zeros_like(g), where=norm > 0), dtype=np.float32)
         return self.normals
 
+    def project(self, geometry, level=0.0, **kw):
+        """Move the vertices onto {geometry = level} in place (surface.project from every vertex; `kw`: its tol,
+        max_iter, relax) and set `normals` from the gradients at the projected points. `faces` stays as it is; a vertex
+        whose status is not CONVERGED stays where it was. -> the SurfacePoints of the vertices."""
+        from .surface import _project_vertices
+        sp, self.vertices, self.normals = _project_vertices(self.vertices, geometry, level, kw, 3)
+        return sp
+
     def write_obj(self, path):
         v = np.asarray(self.vertices, dtype=np.float32)
         with open(path, "w") as f:
@@ -110,14 +118,23 @@ class Mesh:
 
 
 class Contour:
-    """Contour segments: vertices (V, 2) float32, segments (S, 2) int64 with the inside on the left of a -> b."""
+    """Contour segments: vertices (V, 2) float32, segments (S, 2) int64 with the inside on the left of a -> b;
+    normals None, or (V, 3) float32 after project()."""
 
     def __init__(self, vertices, segments):
         self.vertices = vertices
         self.segments = segments
+        self.normals = None
 
     def __repr__(self):
         return "Contour(%d vertices, %d segments)" % (len(self.vertices), len(self.segments))
+
+    def project(self, geometry, level=0.0, **kw):
+        """Mesh.project for a contour: the vertices move in the plane (z is 0 and stays 0: every 2-D rule's z tangent is
+        exactly 0), `normals` (V, 3) float32 is set, `segments` stays as it is. -> the SurfacePoints of the vertices."""
+        from .surface import _project_vertices
+        sp, self.vertices, self.normals = _project_vertices(self.vertices, geometry, level, kw, 2)
+        return sp
 
     def loops(self):
         """The segments chained into polylines of vertex ids: closed loops first (their first vertex repeated at the

@@ -460,6 +460,25 @@ int sdfk_eval_jvp_device(sdfk_program* prog, const float* d_co, int64_t n, int64
 int sdfk_value_jvp_device(int op, const float* P, const float* d_v, const float* d_t, int64_t n, float* d_out_v,
                           float* d_out_t, void* stream);
 
+/* ---- projection onto a level set (aegolius_amd.surface; csrc/sdfk_project.inc) ---------------------------------------
+ * Newton iteration q <- q - relax (f(q) - level) grad f(q) / |grad f(q)|^2 from every input point, value and gradient from
+ * the dual kernel's point mode, all iterations in one launch. Per point: d_q (3 rows q_stride apart) the final point,
+ * d_value the field there, d_grad (3 rows grad_stride apart, may be null) its gradient there, d_start (may be null) the
+ * field at the input point, d_info = status | iterations << 8. Status: 0 converged (|f - level| <= tol), 1 max_iter
+ * steps taken without converging, 2 stalled (|grad f|^2 < 1e-24), 3 the field is not finite. A point that stops keeps
+ * the q it had. max_iter 0 .. 255, tol >= 0, relax in (0, 1], level finite. Programs: those sdfk_program_jvp_check
+ * accepts. Asynchronous on the stream; n == 0 launches nothing. */
+int sdfk_project_points_device(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, float level, float tol,
+                               int max_iter, float relax, float* d_q, int64_t q_stride, float* d_value, float* d_grad,
+                               int64_t grad_stride, float* d_start, int32_t* d_info, void* stream);
+/* The same launch, which also ADDS to d_wg_trips[w] the program evaluations of every wave of workgroup w
+ * (sdfk_project_workgroups(n) counters, zeroed by the caller): what the iteration cost, for measurements. */
+int64_t sdfk_project_workgroups(int64_t n);
+int sdfk_project_points_counted_device(sdfk_program* prog, const float* d_co, int64_t n, int64_t row_stride, float level,
+                                       float tol, int max_iter, float relax, float* d_q, int64_t q_stride, float* d_value,
+                                       float* d_grad, int64_t grad_stride, float* d_start, int32_t* d_info,
+                                       uint32_t* d_wg_trips, void* stream);
+
 /* ---- reverse-mode derivatives (adjoint; csrc/sdfk_adjoint.inc, rules derived from csrc/sdfk_dualdev.h) --------------
  * One pass evaluates the program at n points with a restore tape and back-propagates a cotangent c_i per point; the
  * parameter adjoints P̄_j = sum_i c_i d f_i / d P_j are reduced on the device in float64 (deterministic order).
