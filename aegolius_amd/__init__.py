@@ -16,5 +16,6 @@ from . import render  # noqa: F401
 from . import redistance  # noqa: F401
 from . import enclosure  # noqa: F401
 from . import surface  # noqa: F401
+from . import slices  # noqa: F401
 
 __version__ = "0.1.0"

@@ -138,6 +138,12 @@ SIGNATURES = {
                                         _int]),
     "sdfk_eval_grid_contour2d_finish": (_int, [_vp, _vp, _i64, _vp, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int,
                                                _vp, _vp, _int]),
+    "sdfk_eval_grid_slices_scratch": (_sz, [_i64, _i64, _i64]),
+    "sdfk_eval_grid_slices": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _c.POINTER(_i64), _c.POINTER(_i64), _vp,
+                                     _vp, _int]),
+    "sdfk_eval_grid_slices_finish": (_int, [_vp, _i64, _i64, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp,
+                                            _vp, _vp, _int]),
+    "sdfk_eval_grid_slices_measure": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp, _vp, _vp, _int]),
     "sdfk_program_rays_check": (_int, [_vp, _c.POINTER(_int)]),
     "sdfk_trace_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                       _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
@@ -540,6 +546,68 @@ class Program:
             raise ValueError("mesh_grid: two or three axis tables")
         lead = (self._h,) + tab
         return extract_mesh("sdfk_eval_grid", [a.size for a in ax], level, lead, lead, (mode,), timings)
+
+    def slices_grid(self, tables, level, device=0, mode=MODE_AUTO, timings=None):
+        """Plane stack of {f = level} on the grid of `tables` = (heights, U, V), the layer the slowest axis, WITHOUT a
+        field (sdfk_eval_grid_slices and its _finish): every layer the contour of mesh_grid on its 2-D grid (U, V). The
+        tables must be strictly increasing float32 arrays and `level` not NaN (aegolius_amd.slices checks both).
+        -> (vertices (V, 2) float32 as (a, b), segments (S, 2) int32, or int64 from 2^31 vertices on, vertex offsets and
+        segment offsets (layers + 1,) int64). `timings`: a dict that receives device-event milliseconds of count
+        (evaluation to bits, count, scans, layer offsets) / emit / copy."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(tables)
+        if len(ax) != 3:
+            raise ValueError("slices_grid: the heights and two in-plane tables")
+        shape = [a.size for a in ax]
+        lv = _c.c_float(level)
+        nv, ns = _i64(0), _i64(0)
+        voff, soff = np.zeros(shape[0] + 1, dtype=np.int64), np.zeros(shape[0] + 1, dtype=np.int64)
+        timer = Timer(timings)
+        with contextlib.ExitStack() as stack:
+            def alloc(nbytes):
+                return stack.enter_context(DeviceBuffer(nbytes, what="slices"))
+            timer.mark("start")
+            scratch = alloc(L.sdfk_eval_grid_slices_scratch(*shape))
+            check(L.sdfk_eval_grid_slices(self._h, *tab, lv, ctypes.byref(nv), ctypes.byref(ns), scratch.at(), None, mode),
+                  "sdfk_eval_grid_slices")
+            timer.mark("count")
+            V, S = nv.value, ns.value
+            wide = V > 0x7fffffff
+            d_v = alloc(V * 8)
+            d_s = alloc(S * 2 * (8 if wide else 4))
+            check(L.sdfk_eval_grid_slices_finish(self._h, *shape, lv, V, S, d_v.at(), V, d_s.at(), S, 8 if wide else 4, _ptr(voff),
+                                                 _ptr(soff), scratch.at(), None, mode), "sdfk_eval_grid_slices_finish")
+            timer.mark("emit")
+            verts = d_v.download(np.empty((V, 2), dtype=np.float32))
+            segs = d_s.download(np.empty((S, 2), dtype=np.int64 if wide else np.int32))
+            timer.mark("copy")
+            timer.finish()
+        return verts, segs, voff, soff
+
+    def slices_measure_grid(self, tables, level, device=0, mode=MODE_AUTO, timings=None):
+        """Section measures of the plane stack of slices_grid, reduced per layer on the device
+        (sdfk_eval_grid_slices_measure): the stack never leaves device memory. -> (measures (layers, 6) float64: area,
+        perimeter, first moments in a and b about the rectangle's centre, segments, border crossings; vertex offsets,
+        segment offsets). `timings`: a dict that receives device-event milliseconds of the whole call (measure)."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(tables)
+        if len(ax) != 3:
+            raise ValueError("slices_measure_grid: the heights and two in-plane tables")
+        shape = [a.size for a in ax]
+        out = np.zeros((shape[0], 6), dtype=np.float64)
+        voff, soff = np.zeros(shape[0] + 1, dtype=np.int64), np.zeros(shape[0] + 1, dtype=np.int64)
+        timer = Timer(timings)
+        with DeviceBuffer(L.sdfk_eval_grid_slices_scratch(*shape), what="slices") as scratch:
+            timer.mark("start")
+            check(L.sdfk_eval_grid_slices_measure(self._h, *tab, _c.c_float(level), _ptr(out), _ptr(voff), _ptr(soff), scratch.at(),
+                                                  None, mode), "sdfk_eval_grid_slices_measure")
+            timer.mark("measure")
+            timer.finish()
+        return out, voff, soff
 
     def occupancy_grid(self, axes, sub_tables, half_widths, samples, level, lipschitz, d_out, slab_cells=0, device=0,
                        mode=MODE_AUTO, timings=None):

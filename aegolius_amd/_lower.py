@@ -314,6 +314,17 @@ class Lowerer:
             raise ValueError("rotation matrix must have shape (3, 3); got %r" % (R.shape,))
         t = np.asarray(node.center, dtype=np.float64).reshape(3)
         s = node.scale
+        frame = getattr(node, "frame_map", None)
+        if frame is not None and not (np.array_equal(frame[0], np.eye(3)) and not np.any(frame[1])):
+            # a plane-stack frame (aegolius_amd.slices.Frame.apply): ONE outer XFORM q = A p - c around the unchanged inner
+            # node, never composed with the inner node's own transform (_fold=False keeps it out of emit()'s merge, which
+            # would change the order of the fmas and with it the bits of a section against the geometry's own field)
+            c = self.writable(creg, mode)
+            self.emit("XFORM", c, creg, params=np.concatenate([np.asarray(frame[0], dtype=np.float64).ravel(), frame[1]]),
+                      _fold=False)
+            v = self.lower_expr(node.modified_object, c, OWNED, node._geo_parameters)
+            self.release(c, creg)
+            return v
         pushed = _push_transform_into_members(node) if self.shortcuts else None
         if pushed is not None:
             # a large hard union that was moved / rotated / rescaled as a whole (value modifications on top included):

@@ -552,6 +552,33 @@ int sdfk_eval_grid_contour2d_finish(sdfk_program* prog, const float* ax0, int64_
                                     int64_t n_vertices, int64_t n_segments, float* d_vertices, int64_t vertex_capacity,
                                     void* d_segments, int64_t segment_capacity, int segment_bytes, void* d_scratch,
                                     void* stream, int mode);
+/* Plane stacks: the contours of a PROGRAM on every layer of the grid (heights, u, v) — `layers` >= 1 heights, nu >= 2 and
+ * nv >= 2 in-plane values, all strictly increasing; point (l, i, j) is the program at (heights[l], u[i], v[j]), x from
+ * the slowest axis as everywhere. Layer l is what sdfk_eval_grid_contour2d gives on the 2-D field of that layer with
+ * axes (u, v), bit for bit; the stack's vertices (V, 2) float32 as (a, b) and segments (S, 2) are the layers' one after
+ * the other, vertex ids global; offsets[l] .. offsets[l + 1] is layer l's range (layers + 1 entries, host arrays).
+ * Same two steps as the contour calls: the counting call (evaluation to inside bits, count, scans, layer offsets) returns
+ * V and S, the finishing call takes level and mode of the counting call, writes the arrays (segment_bytes 4 or 8 per
+ * index) and copies the offsets out; while it runs it allocates 32 bytes per vertex. d_scratch: *_scratch bytes (at most
+ * 1 byte per grid point plus O(layers + nu + nv + n / 8192)), 256-byte aligned.
+ * sdfk_eval_grid_slices_measure does both steps in device memory it allocates and frees, then reduces every layer with
+ * one workgroup, in float64 from the float32 vertices relative to the rectangle's centre (ca, cb) and in a fixed order
+ * (no atomics): measures[6 l ..] = area (half the sum of t_s = (a0 - ca)(b1 - cb) - (a1 - ca)(b0 - cb) over the segments
+ * (a0, b0) -> (a1, b1)), perimeter (sum of hypot), first moments (sum of (a0 + a1 - 2 ca) t_s / 6 and the same in b),
+ * the number of segments, and the number of vertices on the border of the rectangle (a == u[0] or u[nu - 1], or
+ * b == v[0] or v[nv - 1]: the contour leaves the grid there). Only the measures and the offsets come back.
+ * Programs with auxiliary fields (staged) are refused. */
+size_t sdfk_eval_grid_slices_scratch(int64_t layers, int64_t nu, int64_t nv);
+int sdfk_eval_grid_slices(sdfk_program* prog, const float* heights, int64_t layers, const float* u, int64_t nu, const float* v,
+                          int64_t nv, float level, int64_t* n_vertices, int64_t* n_segments, void* d_scratch, void* stream,
+                          int mode);
+int sdfk_eval_grid_slices_finish(sdfk_program* prog, int64_t layers, int64_t nu, int64_t nv, float level, int64_t n_vertices,
+                                 int64_t n_segments, float* d_vertices, int64_t vertex_capacity, void* d_segments,
+                                 int64_t segment_capacity, int segment_bytes, int64_t* vertex_offsets,
+                                 int64_t* segment_offsets, void* d_scratch, void* stream, int mode);
+int sdfk_eval_grid_slices_measure(sdfk_program* prog, const float* heights, int64_t layers, const float* u, int64_t nu,
+                                  const float* v, int64_t nv, float level, double* measures, int64_t* vertex_offsets,
+                                  int64_t* segment_offsets, void* d_scratch, void* stream, int mode);
 
 /* ---- sphere tracing ----------------------------------------------------------------------------
  * First hit of rays with the surface of the program's field, which must be a distance bound: |f(p) - f(q)| <=
