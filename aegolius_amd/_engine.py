@@ -144,6 +144,15 @@ SIGNATURES = {
     "sdfk_eval_grid_slices_finish": (_int, [_vp, _i64, _i64, _i64, _c.c_float, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp,
                                             _vp, _vp, _int]),
     "sdfk_eval_grid_slices_measure": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp, _vp, _vp, _int]),
+    "sdfk_label_scratch": (_sz, [_i64, _i64, _i64]),
+    "sdfk_field_label": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _int, _int, _vp, _c.POINTER(_i64), _vp, _fp, _vp]),
+    "sdfk_eval_grid_label": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _int, _int, _vp, _c.POINTER(_i64), _vp, _fp,
+                                    _vp, _int]),
+    "sdfk_label_bits": (_int, [_i64, _i64, _i64, _int, _int, _vp, _c.POINTER(_i64), _vp, _fp, _vp]),
+    "sdfk_label_finish": (_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfk_field_cell_counts": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp]),
+    "sdfk_eval_grid_cell_counts": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp, _int]),
+    "sdfk_label_field": (_int, [_vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _vp, _vp]),
     "sdfk_program_rays_check": (_int, [_vp, _c.POINTER(_int)]),
     "sdfk_trace_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                       _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
@@ -864,6 +873,93 @@ class DeviceField(DeviceBuffer):
         check(lib().sdfk_field_gradient(_vp(self.ptr), shape[0], shape[1], shape[2], 3, 1 if normalize else 0, _vp(out.ptr),
                                         out.stride, None), "sdfk_field_gradient")
         return out
+
+
+CONNECT_FACES, CONNECT_FULL = 0, 1
+REGION_INSIDE, REGION_OUTSIDE = 0, 1
+LABEL_PASSES = ("bits", "init", "merge", "compress", "number")
+
+
+class LabelScratch(DeviceBuffer):
+    """The scratch of the topology calls (sdfk_label_scratch) on the grid of 2 or 3 axis tables: the inside bits of the
+    last source, and the state of the last labelling. aegolius_amd.topology checks the tables and states the definitions.
+    A `source` is a Program (evaluated to inside bits, no field) or a DeviceField of as many values as the grid has
+    points."""
+
+    def __init__(self, tables, device=0):
+        require_gpu()
+        self.tables, tab = axis_args(tables)
+        if len(self.tables) not in (2, 3):
+            raise ValueError("LabelScratch: two or three axis tables")
+        self.shape = tuple(a.size for a in self.tables)
+        self.grid = self.shape + (1,) * (3 - len(self.shape))       # (a 2-D grid is n2 = 1 to the library)
+        self.tab = tab + (None, 1) * (3 - len(self.shape))
+        self.n = int(np.prod(self.shape, dtype=np.int64))
+        DeviceBuffer.__init__(self, lib().sdfk_label_scratch(*self.grid), device, "topology")
+
+    def _source(self, source, mode):
+        if isinstance(source, Program):
+            return "sdfk_eval_grid", (source.handle,), (mode,)
+        source._live()
+        if source.n != self.n:
+            raise ValueError("the field has %d values; the axes span %d points" % (source.n, self.n))
+        return "sdfk_field", (_vp(source.ptr),), ()
+
+    def labels(self):
+        """A DeviceBuffer for the grid's int32 labels, on the scratch's device."""
+        return DeviceBuffer(4 * self.n, self.device, "labels")
+
+    def label(self, source, level, connectivity, region, labels, mode=MODE_AUTO, timings=None):
+        """Label the region of `source` into the DeviceBuffer `labels` (sdfk_field_label / sdfk_eval_grid_label);
+        source None: the inside bits a previous call left in the scratch, without a second evaluation (sdfk_label_bits).
+        -> K. `timings`: a dict that receives device-event milliseconds of LABEL_PASSES."""
+        self._live()
+        L = lib()
+        count = _i64(0)
+        ms = (_c.c_float * len(LABEL_PASSES))() if timings is not None else None
+        d_labels = labels.at(0, 4 * self.n)
+        if source is None:
+            check(L.sdfk_label_bits(*self.grid, int(connectivity), int(region), d_labels, ctypes.byref(count), self.at(), ms, None),
+                  "sdfk_label_bits")
+        else:
+            family, lead, tail = self._source(source, mode)
+            check(getattr(L, family + "_label")(*lead, *self.tab, _c.c_float(level), int(connectivity), int(region), d_labels,
+                                                ctypes.byref(count), self.at(), ms, None, *tail), family + "_label")
+        if timings is not None:
+            for name, value in zip(LABEL_PASSES, ms):
+                timings[name] = timings.get(name, 0.0) + float(value)
+        return int(count.value)
+
+    def records(self, count, labels):
+        """The records of the last labelling (sdfk_label_finish) -> first (K,) int64, sizes (K,) int64, lower and upper
+        (K, D) int32, border (K,) bool."""
+        self._live()
+        K, D = int(count), len(self.shape)
+        first, sizes = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        lower, upper = np.zeros((K, D), dtype=np.int32), np.zeros((K, D), dtype=np.int32)
+        border = np.zeros(K, dtype=np.int32)
+        check(lib().sdfk_label_finish(*self.grid, K, labels.at(0, 4 * self.n), _ptr(first), _ptr(sizes), _ptr(lower), _ptr(upper),
+                                      _ptr(border), self.at(), None), "sdfk_label_finish")
+        return first, sizes, lower, upper, border.astype(bool)
+
+    def cell_counts(self, source, level, mode=MODE_AUTO):
+        """(V, E, F, C) of the cubical complex of the inside points of `source` (sdfk_field_cell_counts /
+        sdfk_eval_grid_cell_counts) as Python ints; the inside bits stay in the scratch."""
+        self._live()
+        counts = np.zeros(4, dtype=np.int64)
+        family, lead, tail = self._source(source, mode)
+        check(getattr(lib(), family + "_cell_counts")(*lead, *self.tab, _c.c_float(level), _ptr(counts), self.at(), None, *tail),
+              family + "_cell_counts")
+        return tuple(int(c) for c in counts)
+
+
+def label_field(labels, n, keep, inside, outside, device=0):
+    """A DeviceField of n values: `inside` where the int32 label in the DeviceBuffer `labels` is an id with keep[id] set
+    (keep: K bools), `outside` elsewhere (sdfk_label_field)."""
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    field = DeviceField(n, device)
+    return field._filled(lambda: check(lib().sdfk_label_field(labels.at(0, 4 * n), n, _ptr(keep), keep.size, float(inside),
+                                                              float(outside), _vp(field.ptr), None), "sdfk_label_field"))
 
 
 def field_row_sums(d_field, rows, row_len, weights):

@@ -580,6 +580,63 @@ int sdfk_eval_grid_slices_measure(sdfk_program* prog, const float* heights, int6
                                   const float* v, int64_t nv, float level, double* measures, int64_t* vertex_offsets,
                                   int64_t* segment_offsets, void* d_scratch, void* stream, int mode);
 
+/* ---- topology: connected components, cell counts, label fields (aegolius_amd.topology; csrc/sdfk_topology.inc) --------
+ * Grid: D = 2 or 3 strictly increasing HOST axis tables of at least 2 points each, points in C order (flat index
+ * p = (i0 n1 + i1) n2 + i2, as the mesh calls); n2 = 1 is a 2-D grid (ax2 is then not read). At most 2^31 - 1 points:
+ * labels are int32. A point is inside iff f <= level, compared as selection keys — the mesh's rule, NaN outside. `region`:
+ * SDFK_REGION_INSIDE labels the inside points, SDFK_REGION_OUTSIDE all the others. `connectivity`: SDFK_CONNECT_FACES joins
+ * the 4 (2-D) / 6 (3-D) neighbours across a grid edge, SDFK_CONNECT_FULL the 8 / 26 neighbours of the surrounding block.
+ * The canonical name of a component is the smallest flat index among its points (`first`); components are numbered
+ * 0 .. K - 1 by ascending `first`, so every output is independent of scheduling. d_labels: n0 n1 n2 int32, DEVICE: the id
+ * of the point's component, -1 where the point is not in the region.
+ * Two steps, as the mesh calls. The labelling call makes the inside bits (sdfk_field_label: from a resident field;
+ * sdfk_eval_grid_label: the flag builds of the evaluation kernels, no field, `mode` as for sdfk_eval_grid_isosurface),
+ * labels them (init from the bits, lock-free union by atomicMin, compress, number; every phase a launch of its own) and
+ * returns *count = K. sdfk_label_bits labels the inside bits a previous call left in the scratch — any of the labelling
+ * or cell-count calls on the same grid — again, with another region or connectivity, without a second evaluation.
+ * sdfk_label_finish, after a labelling call with the same d_labels and scratch, writes the K records to HOST arrays:
+ * first[K] and sizes[K] (points) int64, lower[K D] and upper[K D] int32 (the index bounding box, D entries per record),
+ * border[K] int32 (1 when a point of the component lies on a face of the grid); integer atomics only, so the records
+ * do not depend on the order of the waves. It allocates 24 + 8 D bytes per component while it runs.
+ * sdfk_field_cell_counts / sdfk_eval_grid_cell_counts: counts[4] (HOST) = V, E, F, C — the inside points, the grid edges
+ * with both ends inside, the grid squares with all 4 corners inside, the grid cubes with all 8 corners inside (0 in
+ * 2-D): the cells of the cubical complex the inside points span, Euler characteristic V - E + F - C. They leave the
+ * inside bits in the scratch (sdfk_label_bits).
+ * sdfk_label_field: d_out[p] = inside where d_labels[p] is an id with keep[id] != 0 (keep: HOST, count bytes), outside
+ * elsewhere; n floats, one kernel.
+ * d_scratch: sdfk_label_scratch bytes, 256-byte aligned: the inside bits, the region's bits, root flags and prefixes —
+ * at most 1 byte per point plus O(n0 + n1 + n2 + n / 8192); with the labels 5 bytes per point. pass_ms (nullable):
+ * SDFK_LABEL_PASSES floats that receive device-event milliseconds of bits (the region's complement included), init,
+ * merge, compress, number. Every chase and retry loop on the device carries an iteration cap of n0 n1 n2; a call that
+ * reaches it returns -7 (the algorithm cannot: labels only decrease — the cap turns a defect into an error, not a hang).
+ * -1 and no launch: a NULL pointer, a misaligned field (16 bytes) or scratch, an axis of fewer than 2 points or not
+ * strictly increasing, more than 2^31 - 1 points, a NaN level, an unknown connectivity or region, a scratch that does not
+ * hold the bits (or the labelling) of that grid. Programs with auxiliary fields (staged) are refused: evaluate them to
+ * a field first. Synchronous: the stream is idle on return. */
+#define SDFK_CONNECT_FACES 0
+#define SDFK_CONNECT_FULL 1
+#define SDFK_REGION_INSIDE 0
+#define SDFK_REGION_OUTSIDE 1
+#define SDFK_LABEL_PASSES 5
+size_t sdfk_label_scratch(int64_t n0, int64_t n1, int64_t n2);
+int sdfk_field_label(const float* d_field, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                     int64_t n2, float level, int connectivity, int region, int32_t* d_labels, int64_t* count,
+                     void* d_scratch, float* pass_ms, void* stream);
+int sdfk_eval_grid_label(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                         int64_t n2, float level, int connectivity, int region, int32_t* d_labels, int64_t* count,
+                         void* d_scratch, float* pass_ms, void* stream, int mode);
+int sdfk_label_bits(int64_t n0, int64_t n1, int64_t n2, int connectivity, int region, int32_t* d_labels, int64_t* count,
+                    void* d_scratch, float* pass_ms, void* stream);
+int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t count, const int32_t* d_labels, int64_t* first,
+                      int64_t* sizes, int32_t* lower, int32_t* upper, int32_t* border, void* d_scratch, void* stream);
+int sdfk_field_cell_counts(const float* d_field, const float* ax0, int64_t n0, const float* ax1, int64_t n1, const float* ax2,
+                           int64_t n2, float level, int64_t* counts, void* d_scratch, void* stream);
+int sdfk_eval_grid_cell_counts(sdfk_program* prog, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
+                               const float* ax2, int64_t n2, float level, int64_t* counts, void* d_scratch, void* stream,
+                               int mode);
+int sdfk_label_field(const int32_t* d_labels, int64_t n, const unsigned char* keep, int64_t count, float inside,
+                     float outside, float* d_out, void* stream);
+
 /* ---- sphere tracing ----------------------------------------------------------------------------
  * First hit of rays with the surface of the program's field, which must be a distance bound: |f(p) - f(q)| <=
  * L |p - q| with a finite L the caller knows (aegolius_amd._lower tracks it per program). Per ray, in fp32:
