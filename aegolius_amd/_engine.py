@@ -153,6 +153,7 @@ SIGNATURES = {
     "sdfk_field_cell_counts": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp]),
     "sdfk_eval_grid_cell_counts": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp, _int]),
     "sdfk_label_field": (_int, [_vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _vp, _vp]),
+    "sdfk_label_moments": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_program_rays_check": (_int, [_vp, _c.POINTER(_int)]),
     "sdfk_trace_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                       _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
@@ -960,6 +961,18 @@ def label_field(labels, n, keep, inside, outside, device=0):
     field = DeviceField(n, device)
     return field._filled(lambda: check(lib().sdfk_label_field(labels.at(0, 4 * n), n, _ptr(keep), keep.size, float(inside),
                                                               float(outside), _vp(field.ptr), None), "sdfk_label_field"))
+
+
+def label_moments(labels, shape, count):
+    """The integer moment rows of the `count` components in the int32 DeviceBuffer `labels` of the grid `shape` (2 or 3
+    axis lengths) -> (count, 10) uint64, 2-D: (count, 6) (sdfk_label_moments; aegolius_amd.topology states the sums)."""
+    shape = tuple(int(s) for s in shape)
+    n = int(np.prod(shape, dtype=np.int64))
+    out = np.zeros((int(count), 10 if len(shape) == 3 else 6), dtype=np.uint64)
+    labels._live()
+    check(lib().sdfk_label_moments(*(shape + (1,) * (3 - len(shape))), labels.at(0, 4 * n), int(count), _ptr(out), None, None),
+          "sdfk_label_moments")
+    return out
 
 
 def field_row_sums(d_field, rows, row_len, weights):

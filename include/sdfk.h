@@ -604,6 +604,14 @@ int sdfk_eval_grid_slices_measure(sdfk_program* prog, const float* heights, int6
  * inside bits in the scratch (sdfk_label_bits).
  * sdfk_label_field: d_out[p] = inside where d_labels[p] is an id with keep[id] != 0 (keep: HOST, count bytes), outside
  * elsewhere; n floats, one kernel.
+ * sdfk_label_moments: the integer moments of every component, from the label array alone (16-byte aligned; any array of
+ * -1 and ids below `count` on that grid will do, no scratch of a labelling is needed). sums: HOST, count rows of uint64,
+ *     3-D: N, I0, I1, I2, I00, I01, I02, I11, I12, I22        2-D: N, I0, I1, I00, I01, I11
+ * the sums of 1, i_a and i_a i_b (i_a the index on axis a) over the points whose label is the row's id. One pass over
+ * the labels, row runs in closed form, 64-bit integer adds only: the rows do not depend on the order of the waves. It
+ * allocates 80 (2-D: 48) bytes per component while it runs. d_scratch is not used (the labels are walked directly): pass
+ * NULL. count = 0 returns at once. -2 and no launch: points x (longest axis - 1)^2 >= 2^63, a grid on which a sum could
+ * wrap; -7: a label below -1 or not below count was met — such labels are left out, never used as an index.
  * d_scratch: sdfk_label_scratch bytes, 256-byte aligned: the inside bits, the region's bits, root flags and prefixes —
  * at most 1 byte per point plus O(n0 + n1 + n2 + n / 8192); with the labels 5 bytes per point. pass_ms (nullable):
  * SDFK_LABEL_PASSES floats that receive device-event milliseconds of bits (the region's complement included), init,
@@ -636,6 +644,8 @@ int sdfk_eval_grid_cell_counts(sdfk_program* prog, const float* ax0, int64_t n0,
                                int mode);
 int sdfk_label_field(const int32_t* d_labels, int64_t n, const unsigned char* keep, int64_t count, float inside,
                      float outside, float* d_out, void* stream);
+int sdfk_label_moments(int64_t n0, int64_t n1, int64_t n2, const int32_t* d_labels, int64_t count, uint64_t* sums,
+                       void* d_scratch, void* stream);
 
 /* ---- sphere tracing ----------------------------------------------------------------------------
  * First hit of rays with the surface of the program's field, which must be a distance bound: |f(p) - f(q)| <=
