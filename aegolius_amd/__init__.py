@@ -18,5 +18,6 @@ from . import enclosure  # noqa: F401
 from . import surface  # noqa: F401
 from . import slices  # noqa: F401
 from . import topology  # noqa: F401
+from . import layers  # noqa: F401
 
 __version__ = "0.1.0"

@@ -154,6 +154,13 @@ SIGNATURES = {
     "sdfk_eval_grid_cell_counts": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _vp, _vp, _vp, _int]),
     "sdfk_label_field": (_int, [_vp, _i64, _vp, _i64, _c.c_float, _c.c_float, _vp, _vp]),
     "sdfk_label_moments": (_int, [_i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sdfk_field_layer_label": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _int, _vp, _c.POINTER(_i64), _vp, _fp, _vp]),
+    "sdfk_eval_grid_layer_label": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _c.c_float, _int, _vp, _c.POINTER(_i64), _vp, _fp,
+                                          _vp, _int]),
+    "sdfk_layer_label_bits": (_int, [_i64, _i64, _i64, _int, _vp, _c.POINTER(_i64), _vp, _fp, _vp]),
+    "sdfk_layer_label_finish": (_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfk_layer_links": (_int, [_i64, _i64, _i64, _i64, _vp, _c.POINTER(_i64), _vp, _vp, _vp]),
+    "sdfk_layer_links_finish": (_int, [_i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sdfk_program_rays_check": (_int, [_vp, _c.POINTER(_int)]),
     "sdfk_trace_rays_device": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
                                       _c.c_float, _int, _vp, _vp, _vp, _vp, _i64, _vp, _int]),
@@ -942,6 +949,62 @@ class LabelScratch(DeviceBuffer):
         check(lib().sdfk_label_finish(*self.grid, K, labels.at(0, 4 * self.n), _ptr(first), _ptr(sizes), _ptr(lower), _ptr(upper),
                                       _ptr(border), self.at(), None), "sdfk_label_finish")
         return first, sizes, lower, upper, border.astype(bool)
+
+    # ---- layer graphs (aegolius_amd.layers states the definitions): the grid is (layers, nu, nv) -------------------------
+    def layer_label(self, source, level, connectivity, labels, mode=MODE_AUTO, timings=None):
+        """Label the inside points of `source` layer by layer, in-plane connectivity only (sdfk_field_layer_label /
+        sdfk_eval_grid_layer_label); source None: the inside bits a previous call left in the scratch
+        (sdfk_layer_label_bits). -> K. `timings` as for label()."""
+        self._live()
+        if len(self.shape) != 3:
+            raise ValueError("LabelScratch.layer_label: a stack has three axis tables (heights, U, V)")
+        L = lib()
+        count = _i64(0)
+        ms = (_c.c_float * len(LABEL_PASSES))() if timings is not None else None
+        d_labels = labels.at(0, 4 * self.n)
+        if source is None:
+            check(L.sdfk_layer_label_bits(*self.grid, int(connectivity), d_labels, ctypes.byref(count), self.at(), ms, None),
+                  "sdfk_layer_label_bits")
+        else:
+            family, lead, tail = self._source(source, mode)
+            check(getattr(L, family + "_layer_label")(*lead, *self.tab, _c.c_float(level), int(connectivity), d_labels,
+                                                      ctypes.byref(count), self.at(), ms, None, *tail), family + "_layer_label")
+        if timings is not None:
+            for name, value in zip(LABEL_PASSES, ms):
+                timings[name] = timings.get(name, 0.0) + float(value)
+        return int(count.value)
+
+    def layer_records(self, count, labels):
+        """The records of the last layer labelling (sdfk_layer_label_finish): as records(), `border` by the in-plane
+        rule."""
+        self._live()
+        K = int(count)
+        first, sizes = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        lower, upper = np.zeros((K, 3), dtype=np.int32), np.zeros((K, 3), dtype=np.int32)
+        border = np.zeros(K, dtype=np.int32)
+        check(lib().sdfk_layer_label_finish(*self.grid, K, labels.at(0, 4 * self.n), _ptr(first), _ptr(sizes), _ptr(lower),
+                                            _ptr(upper), _ptr(border), self.at(), None), "sdfk_layer_label_finish")
+        return first, sizes, lower, upper, border.astype(bool)
+
+    def layer_link_count(self, count, labels):
+        """The link pass of the last layer labelling, first half (sdfk_layer_links) -> M, the number of link candidates, and
+        supported (K,) int64."""
+        self._live()
+        K, M = int(count), _i64(0)
+        supported = np.zeros(K, dtype=np.int64)
+        check(lib().sdfk_layer_links(*self.grid, K, labels.at(0, 4 * self.n), ctypes.byref(M), _ptr(supported), self.at(), None),
+              "sdfk_layer_links")
+        return int(M.value), supported
+
+    def layer_link_candidates(self, count, labels, candidates):
+        """The M candidates layer_link_count counted, in word order (sdfk_layer_links_finish) -> child, parent, length (M,)
+        int64 — one row per stretch; a pair may come more than once."""
+        self._live()
+        M = int(candidates)
+        keys, lengths = np.zeros(M, dtype=np.int64), np.zeros(M, dtype=np.int32)
+        check(lib().sdfk_layer_links_finish(*self.grid, int(count), labels.at(0, 4 * self.n), M, _ptr(keys), _ptr(lengths), self.at(),
+                                            None), "sdfk_layer_links_finish")
+        return keys >> 32, keys & 0xffffffff, lengths.astype(np.int64)
 
     def cell_counts(self, source, level, mode=MODE_AUTO):
         """(V, E, F, C) of the cubical complex of the inside points of `source` (sdfk_field_cell_counts /

@@ -1230,6 +1230,7 @@ extern "C" int sdfk_stream_probe(const float* d_co, int64_t n, int64_t row_strid
 #include "sdfk_mesh.inc"
 #include "sdfk_slices.inc"
 #include "sdfk_topology.inc"
+#include "sdfk_layers.inc"
 #include "sdfk_rays.inc"
 #include "sdfk_occupancy.inc"
 #include "sdfk_moments.inc"

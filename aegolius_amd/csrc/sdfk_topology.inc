@@ -30,6 +30,7 @@
 #define TOPO_ERR_CHASE 1u                          // a chase ran longer than the number of points
 #define TOPO_ERR_RETRY 2u                          // a union retried more often than there are points
 #define TOPO_ERR_LABEL 4u                          // a chase met a label that is no ancestor (negative, or above its point)
+#define TOPO_TAG_LAYERED 3ll                       // the tag's second word after a layer labelling (else: region + 1)
 
 // the 32 region bits of points p .. p + 31, zeros before the first point and past the bit string
 static __device__ __forceinline__ unsigned topo_bits_at(const unsigned* __restrict__ bits, long long words, long long p) {
@@ -294,8 +295,9 @@ static __device__ __forceinline__ void topo_flush(const TopoAcc<D>& a, const Top
 
 // reduce: one word per thread, its row runs one after the other (labels are ids by now). `first` comes from the root
 // flags with plain stores: every id has exactly one root. Runs of one component are added up in registers; when all the
-// runs of a wave belong to one component the wave adds once.
-template <int D>
+// runs of a wave belong to one component the wave adds once. INPLANE (sdfk_layers.inc, D = 3): the border is the four
+// in-plane edges of a layer alone — lying in the first or last layer does not count.
+template <int D, bool INPLANE = false>
 __global__ __launch_bounds__(SDFK_TOPO_THREADS) void sdfk_topo_reduce_kernel(const unsigned* __restrict__ rb, const int* __restrict__ label,
                                                                              MeshGeom g, const unsigned long long* __restrict__ blk,
                                                                              const unsigned* __restrict__ rootbits,
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(SDFK_TOPO_THREADS) void sdfk_topo_reduce_kernel(con
             for (int o = 0; o < D - 1; ++o) {
                 acc.lo[o] = min(acc.lo[o], c[o]);
                 acc.hi[o] = max(acc.hi[o], c[o]);
-                if (c[o] == 0 || c[o] == g.d[o] - 1) acc.border = 1u;
+                if ((!INPLANE || o > 0) && (c[o] == 0 || c[o] == g.d[o] - 1)) acc.border = 1u;
             }
             acc.lo[D - 1] = min(acc.lo[D - 1], c[D - 1]);
             acc.hi[D - 1] = max(acc.hi[D - 1], c1);
@@ -804,10 +806,15 @@ static void topo_launch_merge(bool full, const unsigned* rb, const MeshGeom& g, 
         hipLaunchKernelGGL((sdfk_topo_merge_kernel<D, false>), dim3(tiles), dim3(SDFK_TOPO_THREADS), 0, stream, rb, g, label, cap, err);
 }
 
+typedef void (*TopoMerge)(bool full, const unsigned* rb, const MeshGeom& g, int* label, unsigned* err, unsigned tiles,
+                          hipStream_t stream);
+
 // the labelling of the bit string the scratch holds. ev: marked once already (before the bits); the marks made here end
-// the passes bits (the region's bit string included), init, merge, compress, number.
+// the passes bits (the region's bit string included), init, merge, compress, number. `merge`: another merge pass than the
+// grid's own neighbourhood (sdfk_layers.inc: in-plane only); the tag then carries `kind` instead of region + 1.
 static int topo_label(int D, const MeshGeom& g, const TopoScratch& sc, int connectivity, int region, int* d_labels, int64_t* count,
-                      TopoEvents& ev, float* pass_ms, hipStream_t stream, const char* who) {
+                      TopoEvents& ev, float* pass_ms, hipStream_t stream, const char* who, TopoMerge merge = nullptr,
+                      long long kind = 0) {
     if (!d_labels || !count) return fail(-1, std::string(who) + ": bad arguments");
     if (connectivity != SDFK_CONNECT_FACES && connectivity != SDFK_CONNECT_FULL)
         return fail(-1, std::string(who) + ": connectivity is SDFK_CONNECT_FACES or SDFK_CONNECT_FULL");
@@ -824,7 +831,8 @@ static int topo_label(int D, const MeshGeom& g, const TopoScratch& sc, int conne
     if (rc) return rc;
     hipLaunchKernelGGL(sdfk_topo_init_kernel, dim3(tiles), dim3(SDFK_TOPO_THREADS), 0, stream, rb, g, d_labels);
     if ((rc = ev.mark(stream))) return rc;
-    if (D == 3) topo_launch_merge<3>(full, rb, g, d_labels, sc.err, tiles, stream);
+    if (merge) merge(full, rb, g, d_labels, sc.err, tiles, stream);
+    else if (D == 3) topo_launch_merge<3>(full, rb, g, d_labels, sc.err, tiles, stream);
     else topo_launch_merge<2>(full, rb, g, d_labels, sc.err, tiles, stream);
     if ((rc = ev.mark(stream))) return rc;
     hipLaunchKernelGGL(sdfk_topo_compress_kernel, dim3(blocks), dim3(256), 0, stream, d_labels, g.n, g.n, sc.err);
@@ -842,7 +850,7 @@ static int topo_label(int D, const MeshGeom& g, const TopoScratch& sc, int conne
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail(-6, std::string(who) + ": " + hipGetErrorString(e));
     if (err) return fail(-7, std::string(who) + ": an iteration cap was reached on the device (error word " + std::to_string(err) + ")");
-    const long long tag[3] = {g.n, region + 1, (long long)K};
+    const long long tag[3] = {g.n, merge ? kind : region + 1, (long long)K};
     HIPCHK(hipMemcpy(sc.tag, tag, sizeof(tag), hipMemcpyHostToDevice));
     if ((rc = ev.read(pass_ms))) return rc;
     *count = (int64_t)K;
@@ -934,16 +942,16 @@ extern "C" int sdfk_label_bits(int64_t n0, int64_t n1, int64_t n2, int connectiv
     return topo_label(D, g, sc, connectivity, region, d_labels, count, ev, pass_ms, stream, who);
 }
 
-template <int D>
+template <int D, bool INPLANE = false>
 static void topo_launch_reduce(const unsigned* rb, const int* label, const MeshGeom& g, const TopoScratch& sc, long long K,
                                const TopoRecords& rec, hipStream_t stream) {
-    hipLaunchKernelGGL(sdfk_topo_reduce_kernel<D>, dim3((unsigned)sc.m.tiles), dim3(SDFK_TOPO_THREADS), 0, stream, rb, label, g, sc.m.vblk,
-                       sc.rootbits, sc.rootpre, K, rec);
+    hipLaunchKernelGGL((sdfk_topo_reduce_kernel<D, INPLANE>), dim3((unsigned)sc.m.tiles), dim3(SDFK_TOPO_THREADS), 0, stream, rb, label, g,
+                       sc.m.vblk, sc.rootbits, sc.rootpre, K, rec);
 }
 
-extern "C" int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t count, const int32_t* d_labels, int64_t* first,
-                                 int64_t* sizes, int32_t* lower, int32_t* upper, int32_t* border, void* d_scratch, void* stream_) {
-    const char* who = "sdfk_label_finish";
+// the records of the labelling the scratch holds; layered: a layer labelling (sdfk_layers.inc), with the in-plane border
+static int topo_finish(int64_t n0, int64_t n1, int64_t n2, int64_t count, const int32_t* d_labels, int64_t* first, int64_t* sizes,
+                       int32_t* lower, int32_t* upper, int32_t* border, void* d_scratch, void* stream_, bool layered, const char* who) {
     if (!d_scratch || ((uintptr_t)d_scratch & 255)) return fail(-1, std::string(who) + ": the scratch must be 256-byte aligned");
     if (!d_labels || count < 0 || (count && (!first || !sizes || !lower || !upper || !border)))
         return fail(-1, std::string(who) + ": bad arguments");
@@ -958,6 +966,8 @@ extern "C" int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t cou
     long long tag[3];
     if ((rc = topo_tag(sc, g, tag, who))) return rc;
     if (tag[1] < 1 || tag[2] != count) return fail(-1, std::string(who) + ": the scratch does not hold a labelling of that size");
+    if (layered != (tag[1] == TOPO_TAG_LAYERED))
+        return fail(-1, std::string(who) + (layered ? ": the scratch does not hold a layer labelling" : ": the scratch holds a layer labelling"));
     if (count == 0) return 0;
     const long long K = count;
     const size_t b8 = mesh_align((size_t)K * 8), bD = mesh_align((size_t)K * D * 4), b4 = mesh_align((size_t)K * 4);
@@ -974,7 +984,8 @@ extern "C" int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t cou
     HIPCHK(hipMemsetAsync(rec.lower, 0x7f, bD, stream));          // above every index: an axis has at most 2^30 points
     HIPCHK(hipMemsetAsync(rec.upper, 0xff, bD, stream));          // -1
     HIPCHK(hipMemsetAsync(rec.border, 0, b4, stream));
-    if (D == 3) topo_launch_reduce<3>(sc.rb, d_labels, g, sc, K, rec, stream);
+    if (layered) topo_launch_reduce<3, true>(sc.rb, d_labels, g, sc, K, rec, stream);
+    else if (D == 3) topo_launch_reduce<3>(sc.rb, d_labels, g, sc, K, rec, stream);
     else topo_launch_reduce<2>(sc.rb, d_labels, g, sc, K, rec, stream);
     hipError_t e = hipGetLastError();
     static_assert(sizeof(int64_t) == sizeof(long long), "records are copied as they are");
@@ -986,6 +997,11 @@ extern "C" int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t cou
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return fail(-6, std::string(who) + ": " + hipGetErrorString(e));
     return 0;
+}
+
+extern "C" int sdfk_label_finish(int64_t n0, int64_t n1, int64_t n2, int64_t count, const int32_t* d_labels, int64_t* first,
+                                 int64_t* sizes, int32_t* lower, int32_t* upper, int32_t* border, void* d_scratch, void* stream_) {
+    return topo_finish(n0, n1, n2, count, d_labels, first, sizes, lower, upper, border, d_scratch, stream_, false, "sdfk_label_finish");
 }
 
 template <int D>

@@ -49,7 +49,8 @@ exist. A staged tree (grid operators such as conv_averaging) is evaluated to a r
 
 Not here: more than 2^31 - 1 points; more than one GPU; periodic grids; sub-sampled (samples > 1) per-component moments
 (`field(keep=[k])` is a DeviceField, which `moments` does not take: it samples geometries); attributing a cavity to the
-component that encloses it; the layers of a plane stack labelled as separate 2-D problems.
+component that encloses it. The layers of a plane stack labelled as separate 2-D problems, with the links between
+consecutive layers, are in `layers`.
 """
 import numpy as np
 

@@ -647,6 +647,49 @@ int sdfk_label_field(const int32_t* d_labels, int64_t n, const unsigned char* ke
 int sdfk_label_moments(int64_t n0, int64_t n1, int64_t n2, const int32_t* d_labels, int64_t count, uint64_t* sums,
                        void* d_scratch, void* stream);
 
+/* ---- layer graphs: the components of every layer of a plane stack and their links (aegolius_amd.layers;
+ * csrc/sdfk_layers.inc) --------------------------------------------------------------------------------------------------
+ * Grid: the three strictly increasing HOST tables heights (layers >= 2), u (nu >= 2), v (nv >= 2); the layer is the
+ * slowest axis, flat index p = (l nu + i) nv + j; at most 2^31 - 1 points. Inside as in the topology block. Only the inside
+ * points are labelled, and two points are joined only when they are neighbours within one layer (SDFK_CONNECT_FACES: 4,
+ * SDFK_CONNECT_FULL: 8). Names (`first`, the smallest flat index) and ids (ascending `first`) as in the topology block, so
+ * ids ascend with the layer. d_labels: layers nu nv int32, DEVICE, -1 off the inside.
+ * sdfk_field_layer_label / sdfk_eval_grid_layer_label make the inside bits as sdfk_field_label / sdfk_eval_grid_label do
+ * and label them with the passes of the topology block, the merge pass restricted to the backward row of the same layer;
+ * sdfk_layer_label_bits labels the inside bits a previous topology or layer call left in the scratch. *count = K.
+ * sdfk_layer_label_finish: the K records as sdfk_label_finish writes them (D = 3: lower[3 k] == upper[3 k] == the layer),
+ * but border[k] = 1 only when a point of the component has i = 0, i = nu - 1, j = 0 or j = nv - 1: the first and the last
+ * layer are no border. sdfk_label_finish refuses a layer labelling, and this call any other.
+ * Links. overlap(c, q), c in layer l >= 1 and q in layer l - 1, is the number of columns (i, j) that carry c in layer l and
+ * q in layer l - 1. A stretch is a maximal run of such columns within one grid row and one 32-point word of the bit string;
+ * child and parent are constant in it. sdfk_layer_links, after a layer labelling with the same d_labels and scratch, counts
+ * the stretches (*candidates = M) and writes supported[K] (HOST, int64): the sum of overlap(c, .), the points of c with an
+ * inside point directly beneath; 0 in layer 0. sdfk_layer_links_finish writes the M candidates in word order, which does
+ * not depend on scheduling: keys[M] (HOST, int64) = child << 32 | parent and lengths[M] (HOST, int32). A pair may come more
+ * than once: overlap(c, q) is the sum of the lengths of its candidates, and the link list is the sorted unique keys — the
+ * caller's reduction (layers.combine). 64-bit integer adds only. They allocate 8 bytes per component and 12 bytes per
+ * candidate while they run.
+ * d_scratch: sdfk_label_scratch(layers, nu, nv) bytes — the link pass needs nothing more: its per-tile counts and per-word
+ * prefixes (1/8 byte per point) use regions of that layout the labelling leaves alone. pass_ms as in the topology block.
+ * Return codes, refusals and the synchronous contract are those of the topology block: -7 when an iteration cap was
+ * reached, or when sdfk_layer_links met a label that is no id below count; -1 and no launch also for nv = 1 (a 2-D grid),
+ * a scratch that does not hold a layer labelling of that grid and count, or (finish) a link count of that size. Programs
+ * with auxiliary fields (staged) are refused. */
+int sdfk_field_layer_label(const float* d_field, const float* heights, int64_t layers, const float* u, int64_t nu,
+                           const float* v, int64_t nv, float level, int connectivity, int32_t* d_labels, int64_t* count,
+                           void* d_scratch, float* pass_ms, void* stream);
+int sdfk_eval_grid_layer_label(sdfk_program* prog, const float* heights, int64_t layers, const float* u, int64_t nu,
+                               const float* v, int64_t nv, float level, int connectivity, int32_t* d_labels, int64_t* count,
+                               void* d_scratch, float* pass_ms, void* stream, int mode);
+int sdfk_layer_label_bits(int64_t layers, int64_t nu, int64_t nv, int connectivity, int32_t* d_labels, int64_t* count,
+                          void* d_scratch, float* pass_ms, void* stream);
+int sdfk_layer_label_finish(int64_t layers, int64_t nu, int64_t nv, int64_t count, const int32_t* d_labels, int64_t* first,
+                            int64_t* sizes, int32_t* lower, int32_t* upper, int32_t* border, void* d_scratch, void* stream);
+int sdfk_layer_links(int64_t layers, int64_t nu, int64_t nv, int64_t count, const int32_t* d_labels, int64_t* candidates,
+                     int64_t* supported, void* d_scratch, void* stream);
+int sdfk_layer_links_finish(int64_t layers, int64_t nu, int64_t nv, int64_t count, const int32_t* d_labels, int64_t candidates,
+                            int64_t* keys, int32_t* lengths, void* d_scratch, void* stream);
+
 /* ---- sphere tracing ----------------------------------------------------------------------------
  * First hit of rays with the surface of the program's field, which must be a distance bound: |f(p) - f(q)| <=
  * L |p - q| with a finite L the caller knows (aegolius_amd._lower tracks it per program). Per ray, in fp32:
