@@ -320,6 +320,13 @@ def axis_args(axes):
     return ax, tuple(args)
 
 
+def _add_pass_ms(timings, names, ms):
+    """Add the milliseconds a native call wrote to `ms` to the caller's `timings` dict under `names` (None: no dict)."""
+    if timings is not None:
+        for name, value in zip(names, ms):
+            timings[name] = timings.get(name, 0.0) + float(value)
+
+
 def row_stride(n):
     """Floats between the rows of a staged (rows, n) fp32 array: every row starts on a 256-byte line."""
     return (n + 63) // 64 * 64
@@ -626,6 +633,26 @@ class Program:
             timer.finish()
         return out, voff, soff
 
+    def _lattice_args(self, who, axes, sub_tables, half_widths, samples, device, timings):
+        """What occupancy_grid and moments_grid (`who`, in the error texts) share: the device and the checked tables ->
+        (library, the native call's leading arguments up to the half-widths, the grid's shape, the c_float * 3 of the
+        passes' milliseconds or None without `timings`)."""
+        require_gpu()
+        L = lib()
+        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
+        ax, tab = axis_args(axes)
+        if len(ax) != 3 or len(sub_tables) != 3 or len(half_widths) != 3:
+            raise ValueError("%s: three axis, sub-sample and half-width tables" % who)
+        k = [int(samples) if a.size > 1 else 1 for a in ax]
+        sub = [np.ascontiguousarray(t, dtype=np.float32) for t in sub_tables]
+        hw = [np.ascontiguousarray(t, dtype=np.float32) for t in half_widths]
+        for a, s, h, ka in zip(ax, sub, hw, k):
+            if s.shape != (a.size * ka,) or h.shape != (a.size,):
+                raise ValueError("%s: an axis of %d points takes %d sub-samples and %d half-widths; got %r and %r"
+                                 % (who, a.size, a.size * ka, a.size, s.shape, h.shape))
+        lead = (self._h,) + tab + tuple(_ptr(t) for t in sub + hw)
+        return L, lead, [a.size for a in ax], (_c.c_float * 3)() if timings is not None else None
+
     def occupancy_grid(self, axes, sub_tables, half_widths, samples, level, lipschitz, d_out, slab_cells=0, device=0,
                        mode=MODE_AUTO, timings=None):
         """Occupancy fractions of the cells of the grid the three axis tables span (sdfk_eval_grid_occupancy), written to
@@ -634,30 +661,13 @@ class Program:
         `lipschitz`: the bound the skip rule uses (inf: nothing is skipped). aegolius_amd.occupancy builds the tables and
         states the definition. -> (inside sub-samples, near cells) as Python ints. `timings`: a dict that receives
         device-event milliseconds of centre / classify / sample."""
-        require_gpu()
-        L = lib()
-        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
-        ax, tab = axis_args(axes)
-        if len(ax) != 3 or len(sub_tables) != 3 or len(half_widths) != 3:
-            raise ValueError("occupancy_grid: three axis, sub-sample and half-width tables")
-        k = [int(samples) if a.size > 1 else 1 for a in ax]
-        sub = [np.ascontiguousarray(t, dtype=np.float32) for t in sub_tables]
-        hw = [np.ascontiguousarray(t, dtype=np.float32) for t in half_widths]
-        for a, s, h, ka in zip(ax, sub, hw, k):
-            if s.shape != (a.size * ka,) or h.shape != (a.size,):
-                raise ValueError("occupancy_grid: an axis of %d points takes %d sub-samples and %d half-widths; got %r and %r"
-                                 % (a.size, a.size * ka, a.size, s.shape, h.shape))
-        shape = [a.size for a in ax]
+        L, lead, shape, ms = self._lattice_args("occupancy_grid", axes, sub_tables, half_widths, samples, device, timings)
         inside, near = _i64(0), _i64(0)
-        ms = (_c.c_float * 3)() if timings is not None else None
         with DeviceBuffer(L.sdfk_eval_grid_occupancy_scratch(*shape, int(slab_cells)), what="occupancy") as scratch:
-            check(L.sdfk_eval_grid_occupancy(self._h, *tab, *[_ptr(s) for s in sub], *[_ptr(h) for h in hw], int(samples),
-                                             float(level), float(lipschitz), _vp(d_out), scratch.at(), int(slab_cells),
-                                             ctypes.byref(inside), ctypes.byref(near), ms, None, mode),
+            check(L.sdfk_eval_grid_occupancy(*lead, int(samples), float(level), float(lipschitz), _vp(d_out), scratch.at(),
+                                             int(slab_cells), ctypes.byref(inside), ctypes.byref(near), ms, None, mode),
                   "sdfk_eval_grid_occupancy")
-        if timings is not None:
-            for name, value in zip(("centre", "classify", "sample"), ms):
-                timings[name] = timings.get(name, 0.0) + float(value)
+        _add_pass_ms(timings, ("centre", "classify", "sample"), ms)
         return int(inside.value), int(near.value)
 
     def moments_grid(self, axes, sub_tables, half_widths, samples, level, lipschitz, slab_cells=0, device=0, mode=MODE_AUTO,
@@ -667,31 +677,14 @@ class Program:
         aegolius_amd.moments builds the tables, states the definition and turns the sums into physical quantities.
         -> ((N, U0, U1, U2, U00, U01, U02, U11, U12, U22), near cells) as Python ints. `timings`: a dict that receives
         device-event milliseconds of centre / far / sample."""
-        require_gpu()
-        L = lib()
-        check(L.sdfk_set_device(int(device)), "sdfk_set_device")
-        ax, tab = axis_args(axes)
-        if len(ax) != 3 or len(sub_tables) != 3 or len(half_widths) != 3:
-            raise ValueError("moments_grid: three axis, sub-sample and half-width tables")
-        k = [int(samples) if a.size > 1 else 1 for a in ax]
-        sub = [np.ascontiguousarray(t, dtype=np.float32) for t in sub_tables]
-        hw = [np.ascontiguousarray(t, dtype=np.float32) for t in half_widths]
-        for a, s, h, ka in zip(ax, sub, hw, k):
-            if s.shape != (a.size * ka,) or h.shape != (a.size,):
-                raise ValueError("moments_grid: an axis of %d points takes %d sub-samples and %d half-widths; got %r and %r"
-                                 % (a.size, a.size * ka, a.size, s.shape, h.shape))
-        shape = [a.size for a in ax]
+        L, lead, shape, ms = self._lattice_args("moments_grid", axes, sub_tables, half_widths, samples, device, timings)
         words, near = (_c.c_uint64 * 20)(), _i64(0)
-        ms = (_c.c_float * 3)() if timings is not None else None
         nbytes = L.sdfk_eval_grid_moments_scratch(*shape, int(slab_cells))
         with DeviceBuffer(nbytes, what="moments") as scratch:
-            check(L.sdfk_eval_grid_moments(self._h, *tab, *[_ptr(s) for s in sub], *[_ptr(h) for h in hw], int(samples),
-                                           float(level), float(lipschitz), scratch.at(), nbytes, int(slab_cells), words,
-                                           ctypes.byref(near), ms, None, mode),
+            check(L.sdfk_eval_grid_moments(*lead, int(samples), float(level), float(lipschitz), scratch.at(), nbytes,
+                                           int(slab_cells), words, ctypes.byref(near), ms, None, mode),
                   "sdfk_eval_grid_moments")
-        if timings is not None:
-            for name, value in zip(("centre", "far", "sample"), ms):
-                timings[name] = timings.get(name, 0.0) + float(value)
+        _add_pass_ms(timings, ("centre", "far", "sample"), ms)
         return tuple(int(words[2 * t]) + (int(words[2 * t + 1]) << 64) for t in range(10)), int(near.value)
 
     def select_host(self, co, threshold=0.0, device=0, mode=MODE_AUTO):

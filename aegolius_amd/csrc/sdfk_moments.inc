@@ -1,24 +1,22 @@
 // sdfk_moments.inc — mass properties of a program on a grid: the integer moments M = (N, U0, U1, U2, U00, U01, U02, U11,
 // U12, U22) of the inside sub-sample points of sdfk_eval_grid_occupancy's lattice, the sums of 1, u_a and u_a u_b with
-// u_a = 2 (i_a k_a + j_a) + 1 (included at the end of sdfk.hip, after sdfk_occupancy.inc, whose tables, slabs, far rule and
-// count kernel it uses unchanged; the sample pass itself: sdfk_momdev.h; the definition for users: aegolius_amd/moments.py).
-// No per-cell output exists. Slabs of whole rows, three passes per slab:
+// u_a = 2 (i_a k_a + j_a) + 1 (included at the end of sdfk.hip, after sdfk_occupancy.inc, whose request, tables, scratch
+// tail, far rule, count kernel and slab driver — occ_request, occ_open, occ_tail, occ_slabs — it uses unchanged; the
+// sample pass itself: sdfk_momdev.h; the definition for users: aegolius_amd/moments.py). No per-cell output exists. Of
+// the three passes occ_slabs runs per slab, MomSums supplies what differs from occupancy:
 //
-//   1. centre values : as sdfk_eval_grid_occupancy's pass 1.
-//   2. far           : sdfk_occ_classify_kernel<false> counts the near cells of every run of 1024 cells, the selection's
-//      scan turns the counts into offsets, and sdfk_mom_far_kernel decides again (sdfk_occ_near, the same function of the
-//      same inputs: near_cells is the number occupancy reports), writes the near cells' indices to the list and adds up,
+//   1. centre values : occ_slabs'.
+//   2. far           : after occ_slabs' count and scan, sdfk_mom_far_kernel decides again (sdfk_occ_near, the same function
+//      of the same inputs: near_cells is the number occupancy reports), writes the near cells' indices to the list and adds up,
 //      over the far cells on the inside, the sums of 1, i_a and i_a i_b of their CELL indices. The block sums of 1, u_a
 //      and u_a u_b over the k^d samples of a cell are polynomials of degree two in (i0, i1, i2), so the host expands the
 //      ten index sums into the far cells' share of M in 128-bit integers (mom_expand_far): no field evaluation, and the
 //      device multiplies indices, not lattice coordinates.
 //   3. sample        : sdfk_mom_sample over the list — the interpreter kernel below or the specialised flavour
 //      (SDFK_FL_MOMENTS), same text, same integers.
-// Without a finite bound, and under SDFK_MODE_NOCULL, passes 1 and 2 are left out and pass 3 takes every cell.
 // Both reductions keep per-lane 64-bit sums, fold them once per wave and store one partial of ten uint64 per wave with
 // plain vector stores; the host adds the partials in 128 bits. mom_waves picks the number of waves so that no partial can
-// wrap, and the call fails where none does. Scratch: the two partial arrays, then counts, centre values and list as
-// sdfk_eval_grid_occupancy lays them out.
+// wrap, and the call fails where none does. Scratch: the two partial arrays, then the lattice's tail (occ_tail).
 #include "sdfk_momdev.h"
 
 template <int NC, int NV, typename SRC>
@@ -105,12 +103,11 @@ static size_t mom_partial_bytes(int64_t units) {
     return occ_align((size_t)mom_blocks(waves) * (SDFK_OCC_BLOCK / 64) * SDFK_MOM_SUMS * 8);
 }
 
-// scratch layout: the sample pass's partials | the far pass's partials | (runs + 1) counts / offsets | centre values | list
+// scratch layout: the sample pass's partials | the far pass's partials | the lattice's tail
 extern "C" size_t sdfk_eval_grid_moments_scratch(int64_t n0, int64_t n1, int64_t n2, int64_t slab_cells) {
     if (n0 < 1 || n1 < 1 || n2 < 1) return 0;
     const int64_t slab = occ_slab_cells(n0, n1, n2, slab_cells);
-    return mom_partial_bytes(slab) + mom_partial_bytes(occ_runs(slab)) + occ_align((size_t)(occ_runs(slab) + 1) * 8) +
-           2 * occ_align((size_t)slab * 4);
+    return mom_partial_bytes(slab) + mom_partial_bytes(occ_runs(slab)) + occ_tail_bytes(slab);
 }
 
 // sum[t] += the partials of `waves` waves (device -> host; synchronises the stream)
@@ -143,178 +140,81 @@ static void mom_expand_far(const mom_u128* I, const unsigned* k, mom_u128* M) {
     }
 }
 
+// occ_slabs' consumer: the far cells' index sums from the second classify pass, the near cells' share of M from the sample
+// pass. Each reduction is sized so that no partial can wrap (the weights and caps: sdfk_eval_grid_moments) and folded on
+// the host, which is also the stream synchronisation occ_slabs asks for.
+struct MomSums {
+    const std::string& w;
+    mom_u128 group_weight, run_weight;
+    unsigned cap_groups, cap_runs;
+    unsigned long long* d_part_near;
+    unsigned long long* d_part_far;
+    mom_u128 far_sum[SDFK_MOM_SUMS] = {}, M[SDFK_MOM_SUMS] = {};
+    std::vector<unsigned long long> host;
+    unsigned far_waves = 0, waves = 0;
+    template <int NC, int NV, typename SRC>
+    static auto interp_kernel() { return sdfk_mom_interp_kernel<NC, NV, SRC>; }
+    int classify(const OccTables& t, const OccTail& s, int64_t, long long runs, unsigned) {
+        far_waves = mom_waves((unsigned long long)runs, run_weight, cap_runs);
+        if (!far_waves) return fail(-2, w + ": a 64-bit partial sum could wrap");
+        far_waves = mom_blocks(far_waves) * (SDFK_OCC_BLOCK / 64);
+        hipLaunchKernelGGL(sdfk_mom_far_kernel, dim3(far_waves / (SDFK_OCC_BLOCK / 64)), dim3(SDFK_OCC_BLOCK), 0, t.x.stream,
+                           (const float*)s.d_centre, t.C, s.d_list, (const unsigned long long*)s.d_blk, runs, far_waves, d_part_far);
+        return 0;
+    }
+    int classified(hipStream_t stream) { return mom_add_partials(d_part_far, far_waves, stream, &host, far_sum); }
+    template <typename SRC>
+    int sample(const OccRequest& q, const OccTables& t, SRC src, int64_t) {
+        const unsigned long long groups = (src.n + q.per_wave - 1) / q.per_wave;
+        waves = mom_waves(groups, group_weight, cap_groups);
+        if (!waves) return fail(-2, w + ": a 64-bit partial sum could wrap");
+        const unsigned blocks = mom_blocks(waves);
+        waves = blocks * (SDFK_OCC_BLOCK / 64);
+        return occ_sample_launch<MomSums>(q, t, src, blocks, waves, d_part_near);
+    }
+    int sampled(hipStream_t stream) { return mom_add_partials(d_part_near, waves, stream, &host, M); }
+};
+
 extern "C" int sdfk_eval_grid_moments(sdfk_program* p, const float* ax0, int64_t n0, const float* ax1, int64_t n1,
                                       const float* ax2, int64_t n2, const float* sub0, const float* sub1, const float* sub2,
                                       const float* hw0, const float* hw1, const float* hw2, int samples, float level,
                                       float lipschitz, void* d_scratch, size_t scratch_bytes, int64_t slab_cells,
                                       uint64_t* moments_out, int64_t* near_cells, float* pass_ms, void* stream_, int mode) {
     const std::string w = "sdfk_eval_grid_moments";
-    if (!p) return fail(-1, "null program");
-    if (!ax0 || !ax1 || !ax2 || !sub0 || !sub1 || !sub2 || !hw0 || !hw1 || !hw2) return fail(-1, w + ": null table");
-    if (n0 < 1 || n1 < 1 || n2 < 1 || n1 > 0x7fffffff || n2 > 0x7fffffff || n0 > 0x7fffffff)
-        return fail(-1, w + ": axis sizes from 1 to 2^31 - 1");
-    if (samples != 1 && samples != 2 && samples != 4 && samples != 8) return fail(-1, w + ": samples per axis: 1, 2, 4 or 8");
-    if (occ_is_nan(level)) return fail(-1, w + ": the level is NaN");
-    if (occ_is_nan(lipschitz) || lipschitz < 0.0f) return fail(-1, w + ": the Lipschitz bound must not be negative or NaN");
+    OccRequest q = {p, {ax0, ax1, ax2}, {sub0, sub1, sub2}, {hw0, hw1, hw2}, {n0, n1, n2}, samples, level, lipschitz, slab_cells, mode};
+    int rc = occ_request(w, 0x7fffffff, &q);
+    if (rc) return rc;
     if (!d_scratch) return fail(-1, w + ": null scratch pointer");
     if (!moments_out || !near_cells) return fail(-1, w + ": null result pointer");
-    if (mode < SDFK_MODE_AUTO || mode > SDFK_MODE_NOCULL) return fail(-1, w + ": unknown mode");
     if (scratch_bytes < sdfk_eval_grid_moments_scratch(n0, n1, n2, slab_cells)) return fail(-1, w + ": the scratch buffer is too small");
-    int bad = -1;
-    const int chk = sdfk_program_rays_check(p, &bad);
-    if (chk) return fail(chk < 0 ? chk : -3, w + ": " + g_err);
-    if (mode == SDFK_MODE_AUTO) mode = g_default_mode;
-    const bool skip = occ_is_finite(lipschitz) && mode != SDFK_MODE_NOCULL;
-
-    const unsigned k[3] = {n0 > 1 ? (unsigned)samples : 1u, n1 > 1 ? (unsigned)samples : 1u, n2 > 1 ? (unsigned)samples : 1u};
-    const unsigned k0 = k[0], k1 = k[1], k2 = k[2];
-    auto lg = [](unsigned k) { return k == 8 ? 3u : k == 4 ? 2u : k == 2 ? 1u : 0u; };
-    const unsigned K = k0 * k1 * k2;
-    const int64_t total_cells = n0 * n1 * n2;
-    const int64_t slab = occ_slab_cells(n0, n1, n2, slab_cells);
     // the longest axis in sub-samples: u = 2 (i k + j) + 1 < 2 n k is computed in 32 bits on the device
-    const int64_t longest = std::max(std::max(n0 * k0, n1 * k1), n2 * k2);
+    const int64_t longest = std::max(std::max(n0 * q.k[0], n1 * q.k[1]), n2 * q.k[2]);
     if (longest >= (1LL << 31)) return fail(-1, w + ": an axis of 2^31 sub-samples or more");
-    const unsigned per_group = K >= 64u ? 1u : 64u / K;         // entries of one group (sdfk_momdev.h)
+    const int64_t slab = q.slab;
     const mom_u128 u_max = 2 * (mom_u128)longest;
-    const mom_u128 group_weight = (mom_u128)std::max(K, 64u) * u_max * u_max;
+    const mom_u128 group_weight = (mom_u128)std::max(q.K, 64u) * u_max * u_max;
     const mom_u128 run_weight = (mom_u128)SDFK_OCC_RUN * (mom_u128)longest * (mom_u128)longest;
-    const unsigned long long slab_groups = ((unsigned long long)slab + per_group - 1) / per_group;
+    const unsigned long long slab_groups = ((unsigned long long)slab + q.per_wave - 1) / q.per_wave;
     // (groups and runs of a slab never exceed these; the partial arrays are laid out for them)
     const unsigned cap_groups = (unsigned)std::min<int64_t>(slab, SDFK_MOM_WAVES_MAX);
     const unsigned cap_runs = (unsigned)std::min<int64_t>(occ_runs(slab), SDFK_MOM_WAVES_MAX);
-    if (!mom_waves(slab_groups, group_weight, cap_groups) || (skip && !mom_waves((unsigned long long)occ_runs(slab), run_weight, cap_runs)))
+    if (!mom_waves(slab_groups, group_weight, cap_groups) || (q.skip && !mom_waves((unsigned long long)occ_runs(slab), run_weight, cap_runs)))
         return fail(-2, w + ": a 64-bit partial sum could wrap on a grid this long (take smaller slabs)");
 
-    LaunchCtx x;
-    int rc = launch_ctx(p, stream_, &x);
+    OccTables t;
+    rc = occ_open(q, stream_, SDFK_FL_MOMENTS, "moments kernel", &t);
     if (rc) return rc;
-    hipStream_t stream = x.stream;
-    // the sample pass's kernel, the same for every slab (a failed build falls back in AUTO only)
-    std::shared_ptr<SpecModule> sk;
-    rc = pick_kernel(p, x.device, SDFK_FL_MOMENTS, 0, mode, mode == SDFK_MODE_AUTO, "moments kernel", false, &sk);
-    if (rc) return rc;
-
-    // tables: as sdfk_eval_grid_occupancy uploads them
-    AxisTables axes, extra;
-    SrcGrid g;
-    rc = upload_axes(ax0, n0, ax1, n1, ax2, n2, stream, &axes, &g, 0);
-    if (rc) return rc;
-    const size_t s0 = (size_t)n0 * k0, s1 = (size_t)n1 * k1, s2 = (size_t)n2 * k2;
-    HIPCHK(hipMalloc(&extra.d, (s0 + s1 + s2 + (size_t)(n0 + n1 + n2)) * sizeof(float)));
-    float* d_sub[3] = {extra.d, extra.d + s0, extra.d + s0 + s1};
-    float* d_hw[3] = {extra.d + s0 + s1 + s2, extra.d + s0 + s1 + s2 + n0, extra.d + s0 + s1 + s2 + n0 + n1};
-    HIPCHK(hipMemcpyAsync(d_sub[0], sub0, s0 * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_sub[1], sub1, s1 * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_sub[2], sub2, s2 * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_hw[0], hw0, (size_t)n0 * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_hw[1], hw1, (size_t)n1 * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_hw[2], hw2, (size_t)n2 * sizeof(float), hipMemcpyHostToDevice, stream));
-
     char* scratch = (char*)d_scratch;
-    unsigned long long* d_part_near = (unsigned long long*)scratch;
-    unsigned long long* d_part_far = (unsigned long long*)(scratch + mom_partial_bytes(slab));
-    char* rest = scratch + mom_partial_bytes(slab) + mom_partial_bytes(occ_runs(slab));
-    unsigned long long* d_blk = (unsigned long long*)rest;
-    rest += occ_align((size_t)(occ_runs(slab) + 1) * 8);
-    float* d_centre = (float*)rest;
-    unsigned* d_list = (unsigned*)(rest + occ_align((size_t)slab * 4));
-
-    OccEvents ev;
-    if (pass_ms) {
-        for (hipEvent_t& e : ev.e) HIPCHK(hipEventCreate(&e));
-        pass_ms[0] = pass_ms[1] = pass_ms[2] = 0.0f;
+    const size_t near_bytes = mom_partial_bytes(slab), far_bytes = mom_partial_bytes(occ_runs(slab));
+    MomSums sums = {w, group_weight, run_weight, cap_groups, cap_runs, (unsigned long long*)scratch,
+                    (unsigned long long*)(scratch + near_bytes)};
+    rc = occ_slabs(w, q, t, occ_tail(scratch + near_bytes + far_bytes, slab), pass_ms, sums, near_cells);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(t.x.stream));                   // the tables are freed on return
+    mom_expand_far(sums.far_sum, q.k, sums.M);
+    for (int i = 0; i < SDFK_MOM_SUMS; ++i) {
+        moments_out[2 * i] = (uint64_t)sums.M[i];
+        moments_out[2 * i + 1] = (uint64_t)(sums.M[i] >> 64);
     }
-    sdfk_occgrid G = {d_sub[0], d_sub[1], d_sub[2], (unsigned)n1, (unsigned)n2, k1, k2, k0, lg(k1), lg(k2), K,
-                      lg(k0) + lg(k1) + lg(k2), 1.0f / (float)K, sdfk_sel_key(level), total_cells < (1LL << 32) ? 1u : 0u, 0};
-    sdfk_occclass C = {g.ax0, g.ax1, g.ax2, d_hw[0], d_hw[1], d_hw[2], (unsigned)n1, (unsigned)n2, 0, 0, level, lipschitz,
-                       sdfk_sel_key(level)};
-    const float* prm = x.prm;
-    const float* tab = x.tab;
-    int64_t near_total = 0;
-    mom_u128 far_sum[SDFK_MOM_SUMS] = {}, M[SDFK_MOM_SUMS] = {};
-    std::vector<unsigned long long> host;
-
-    for (int64_t first = 0; first < total_cells; first += slab) {
-        const int64_t cells = std::min(slab, total_cells - first);
-        unsigned long long n_entries = (unsigned long long)cells;
-        unsigned far_waves = 0;
-        if (pass_ms) HIPCHK(hipEventRecord(ev.e[0], stream));
-        if (skip) {
-            g.start = first;
-            rc = run(grid_call(p, &g, cells, d_centre, stream, mode, true));
-            if (rc) return rc;
-            if (pass_ms) HIPCHK(hipEventRecord(ev.e[1], stream));
-            C.first = first;
-            C.count = cells;
-            const long long runs = occ_runs(cells);
-            const unsigned blocks = (unsigned)((runs + SDFK_OCC_BLOCK / 64 - 1) / (SDFK_OCC_BLOCK / 64));
-            hipLaunchKernelGGL(sdfk_occ_classify_kernel<false>, dim3(blocks), dim3(SDFK_OCC_BLOCK), 0, stream,
-                               (const float*)d_centre, C, (float*)nullptr, d_list, d_blk);
-            hipLaunchKernelGGL(sdfk_select_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blk, runs);
-            far_waves = mom_waves((unsigned long long)runs, run_weight, cap_runs);
-            if (!far_waves) return fail(-2, w + ": a 64-bit partial sum could wrap");
-            far_waves = mom_blocks(far_waves) * (SDFK_OCC_BLOCK / 64);
-            hipLaunchKernelGGL(sdfk_mom_far_kernel, dim3(far_waves / (SDFK_OCC_BLOCK / 64)), dim3(SDFK_OCC_BLOCK), 0, stream,
-                               (const float*)d_centre, C, d_list, (const unsigned long long*)d_blk, runs, far_waves, d_part_far);
-            HIPCHK(hipGetLastError());
-            unsigned long long h = 0;
-            HIPCHK(hipMemcpyAsync(&h, d_blk + runs, sizeof h, hipMemcpyDeviceToHost, stream));
-            rc = mom_add_partials(d_part_far, far_waves, stream, &host, far_sum);
-            if (rc) return rc;
-            if (h > (unsigned long long)cells) return fail(-2, w + ": the list of near cells is longer than the slab");
-            n_entries = h;
-        } else if (pass_ms) {
-            HIPCHK(hipEventRecord(ev.e[1], stream));
-        }
-        if (pass_ms) HIPCHK(hipEventRecord(ev.e[2], stream));
-        near_total += (int64_t)n_entries;
-        if (n_entries) {
-            G.first = first;
-            const unsigned long long groups = (n_entries + per_group - 1) / per_group;
-            unsigned waves = mom_waves(groups, group_weight, cap_groups);
-            if (!waves) return fail(-2, w + ": a 64-bit partial sum could wrap");
-            const unsigned blocks = mom_blocks(waves);
-            waves = blocks * (SDFK_OCC_BLOCK / 64);
-            SdfkOccList src_list = {d_list, n_entries};
-            SdfkOccAll src_all = {n_entries};
-            if (sk) {
-                void* src = skip ? (void*)&src_list : (void*)&src_all;
-                void* args[] = {&prm, &tab, src, &G, &waves, &d_part_near};
-                HIPCHK(hipModuleLaunchKernel(sk->fn[skip ? 0 : 1], blocks, 1, 1, SDFK_OCC_BLOCK, 1, 1, 0, stream, args, nullptr));
-            } else {
-                auto launch = [&](auto src) {
-                    using SRC = decltype(src);
-#define SDFK_MOM_GO(NC, NV) hipLaunchKernelGGL((sdfk_mom_interp_kernel<NC, NV, SRC>), dim3(blocks), dim3(SDFK_OCC_BLOCK), 0, stream, \
-                                               x.d->d_code, x.n_instr, prm, tab, x.result_reg, src, G, waves, d_part_near)
-                    SDFK_REGFILE(p, SDFK_NC, SDFK_NV, SDFK_MOM_GO);
-#undef SDFK_MOM_GO
-                };
-                if (skip) launch(src_list);
-                else launch(src_all);
-                HIPCHK(hipGetLastError());
-            }
-            if (pass_ms) HIPCHK(hipEventRecord(ev.e[3], stream));
-            rc = mom_add_partials(d_part_near, waves, stream, &host, M);
-            if (rc) return rc;
-        } else if (pass_ms) {
-            HIPCHK(hipEventRecord(ev.e[3], stream));
-        }
-        if (pass_ms) {
-            HIPCHK(hipEventSynchronize(ev.e[3]));
-            for (int i = 0; i < 3; ++i) {
-                float ms = 0.0f;
-                HIPCHK(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
-                pass_ms[i] += ms;
-            }
-        }
-    }
-    HIPCHK(hipStreamSynchronize(stream));                       // the tables are freed on return
-    mom_expand_far(far_sum, k, M);
-    for (int t = 0; t < SDFK_MOM_SUMS; ++t) {
-        moments_out[2 * t] = (uint64_t)M[t];
-        moments_out[2 * t + 1] = (uint64_t)(M[t] >> 64);
-    }
-    *near_cells = near_total;
     return 0;
 }

@@ -49,11 +49,9 @@ on the interpreter kernel while the specialised one builds; all give the same in
 """
 import numpy as np
 
-from . import _engine
 from ._eval import config
 from .mesh import _level
-from .occupancy import _axes, _check_samples, _lipschitz, _not_below, _sample_tables
-from .render import _program, lower
+from .occupancy import _axes, _check_samples, _lattice
 
 PAIRS_3D = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 PAIRS_2D = ((0, 0), (0, 1), (1, 1))
@@ -157,18 +155,7 @@ def moments(geometry, axes, samples=4, level=0.0, lipschitz=None, density=1.0, t
     rho = _density(density)
     given, dims = _axes(axes)
     lo, step = _uniform(given)
-    tables, half, _width = _sample_tables(given, k)
-    low, _first = lower(geometry)                               # UnsupportedOpError for staged trees
-    L = _lipschitz(low, lipschitz)
-    prog = _program(low)                                        # UnsupportedOpError for programs that read a field
-    _engine.require_gpu()
-    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in given]
-    if dims == 2:
-        ax.append(np.zeros(1, dtype=np.float32))
-        tables = tables + [np.zeros(1, dtype=np.float32)]
-        half = half + [np.zeros(1, dtype=np.float32)]
-    shape = tuple(a.size for a in ax[:dims])
-    L32 = float(_not_below(np.array([L]))[0]) if np.isfinite(L) else float("inf")
+    prog, ax, tables, half, _width, shape, L32 = _lattice(geometry, given, dims, k, lipschitz)
     M, near = prog.moments_grid(ax, tables, half, k, lv, L32, slab_cells=_slab_cells, device=config.device, mode=config.mode,
                                 timings=timings)
     if dims == 2:                                               # (the third axis has u = 1: U2 = N, U02 = U0, ...)

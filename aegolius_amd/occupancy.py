@@ -165,6 +165,26 @@ def _lipschitz(low, lipschitz):
     return given(lipschitz)
 
 
+def _lattice(geometry, given, dims, k, lipschitz):
+    """What fractions() and moments.moments() do once their arguments are checked, in the order in which things are
+    refused: sub-sample tables, lowering, Lipschitz bound, program, GPU -> (program; float32 axis, sub-sample and
+    half-width tables, three of each — a 2-D grid gets a single-point third axis —; the cell widths per axis given
+    (float64); the grid's shape; the bound as a float32 not below it, or inf)."""
+    tables, half, width = _sample_tables(given, k)
+    low, _first = lower(geometry)                               # UnsupportedOpError for staged trees
+    L = _lipschitz(low, lipschitz)
+    prog = _program(low)                                        # UnsupportedOpError for programs that read a field
+    _engine.require_gpu()
+    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in given]
+    shape = tuple(a.size for a in ax)
+    if dims == 2:
+        ax.append(np.zeros(1, dtype=np.float32))
+        tables = tables + [np.zeros(1, dtype=np.float32)]
+        half = half + [np.zeros(1, dtype=np.float32)]
+    L32 = float(_not_below(np.array([L]))[0]) if np.isfinite(L) else float("inf")
+    return prog, ax, tables, half, width, shape, L32
+
+
 def fractions(geometry, axes, samples=4, level=0.0, lipschitz=None, resident=False, timings=None, _slab_cells=0):
     """Occupancy fractions of `geometry` on the cells of the grid `axes` span (see the module text) -> Occupancy.
     `samples`: k sub-samples per axis (1, 2, 4, 8); `level`: the solid is {f <= level}; `lipschitz`: None = the bound the
@@ -175,19 +195,8 @@ def fractions(geometry, axes, samples=4, level=0.0, lipschitz=None, resident=Fal
     k = _check_samples(samples)
     lv = _level(level)
     given, dims = _axes(axes)
-    tables, half, width = _sample_tables(given, k)
-    low, _first = lower(geometry)                               # UnsupportedOpError for staged trees
-    L = _lipschitz(low, lipschitz)
-    prog = _program(low)                                        # UnsupportedOpError for programs that read a field
-    _engine.require_gpu()
-    ax = [np.ascontiguousarray(a, dtype=np.float32) for a in given]
-    if dims == 2:
-        ax.append(np.zeros(1, dtype=np.float32))
-        tables = tables + [np.zeros(1, dtype=np.float32)]
-        half = half + [np.zeros(1, dtype=np.float32)]
-    shape = tuple(a.size for a in ax[:dims])
+    prog, ax, tables, half, width, shape, L32 = _lattice(geometry, given, dims, k, lipschitz)
     n = int(np.prod(shape))
-    L32 = float(_not_below(np.array([L]))[0]) if np.isfinite(L) else float("inf")
     field = _engine.DeviceField(n, config.device)
     try:
         inside, near = prog.occupancy_grid(ax, tables, half, k, lv, L32, field.ptr, slab_cells=_slab_cells,

@@ -242,6 +242,17 @@ def test_native_argument_checks(built):
     assert L.sdfk_eval_grid_moments_scratch(0, 5, 5, 0) == 0
 
 
+@pytest.mark.parametrize("shape,slab_cells,cells", [((5, 5, 5), 0, 125), ((17, 17, 17), 2000, 117 * 17), ((3, 130, 1), 0, 390)])
+def test_both_entries_carve_the_same_scratch_tail(built, shape, slab_cells, cells):
+    """After their own heads — moments' two partial arrays (the formula of test_native_argument_checks), occupancy's 32 KB —
+    the two entries lay out one tail: the sizes differ by the heads alone. cells: the slab, whole rows."""
+    def partials(units):
+        return (-(-min(units, 65536) // 4) * 4 * 80 + 255) // 256 * 256
+    L = built.lib()
+    got = L.sdfk_eval_grid_moments_scratch(*shape, slab_cells) - L.sdfk_eval_grid_occupancy_scratch(*shape, slab_cells)
+    assert got == partials(cells) + partials(-(-cells // 1024)) - 32768
+
+
 def test_new_entries_are_declared_and_exported(built):
     header = open(os.path.join(ROOT, "include", "sdfk.h")).read()
     for name in ("sdfk_eval_grid_moments_scratch", "sdfk_eval_grid_moments"):
